@@ -8,7 +8,14 @@ same launch.  `--method fabrik` measures configs[2] (FABRIK, tol 1e-3 /
 inputs already resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--method ann|fabrik]
-                    [--total-points T] [--gather 0|1]
+                    [--total-points T] [--gather 0|1] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs
+if --dump-outputs is given and prints the line.  --full adds everything else the
+bench measures or checks: the per-kernel timings and rooflines, the FK-error
+p99, the other methods and modes under 'secondary', FABRIK's cold calls, the
+end-to-end (host-pointer) leg, the CPU baselines with their parity, and at
+N > 1 the gather check and the strong legs.
 
 N > 1 runs one process per GPU: `python bench.py --gpus N` starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` itself as a
@@ -136,7 +143,50 @@ def parse(argv=None):
                          "round trip) and configs[4] (FABRIK tol 1e-5 / 200) as BASELINE.json "
                          "states them, the 10M-point seed-1 batch sharded over the N ranks, "
                          "under 'secondary' (VERDICT r04 #1)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the per-kernel timings and "
+                         "rooflines, the FK-error p99, the secondary methods and modes, the cold "
+                         "and end-to-end legs, the CPU baselines and their parity, the N>1 gather "
+                         "check and strong legs; --secondary, --cpu-seconds, --end-to-end, --cold "
+                         "and --strong-legs apply only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline method's last timed "
+                         "step returned as DIR/<name>.npy (rank 0; float32 / float64, a fixed "
+                         "seeded sample of rows where they exceed 60 MiB)")
     return ap.parse_args(argv)
+
+
+def plain(args):
+    """A run without --full does only what the headline figure needs: the legs
+    beside it are off whatever their options say."""
+    if not args.full:
+        args.secondary = args.end_to_end = args.cold = args.strong_legs = 0
+        args.cpu_seconds = 0.0
+    return args
+
+
+DUMP_BYTES = 60 << 20  # --dump-outputs: the most all the arrays may take together
+
+
+def dump_outputs(outdir, outputs):
+    """Write {name: device array, one row per point} as outdir/<name>.npy: float32
+    stays, everything else becomes float64 (the iteration counts are exact in
+    it).  Arrays that together exceed DUMP_BYTES are cut to the same seeded
+    sample of rows, in row order."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    n = min(v.shape[0] for v in outputs.values())
+    row = sum((v[0].numel() if v.ndim > 1 else 1) * (4 if v.dtype == torch.float32 else 8)
+              for v in outputs.values())
+    keep = None
+    if n * row > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // row, replace=False))
+        keep = torch.from_numpy(keep).to(next(iter(outputs.values())).device)
+    for name, v in outputs.items():
+        v = v[:n] if keep is None else v[keep]
+        a = v.cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"),
+                a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 def open_sharded(ctx, world, rank, sharded=None, unique_id=None):
@@ -493,6 +543,36 @@ def _host_fabrik(job, hp, pinned, tol, max_iter):
     job.ctx._check(rc)
 
 
+def _ann_roofline(job, args, res, m, mode):
+    """The ANN leg's roofline entry (--full: it needs the per-kernel timings)."""
+    flop_pt = m.flops_per_point()
+    kname = "ann_fused_kernel" if mode == "fp32" else f"ann_fused_kernel_{mode}"
+    k = res["kernels"].get(kname)
+    n = job.n_local
+    # split modes: k bf16 / fp16 MFMA products per fp32 product, so the
+    # fp32-equivalent matrix peak is the 16-bit peak / k (the input and output
+    # layers stay fp32)
+    peak = (FP32_MFMA_PEAK if mode == "fp32" else
+            (BF16_MFMA_PEAK if mode == "bf16x6" else FP16_MFMA_PEAK) / SPLIT_PRODUCTS[mode])
+    traffic = load_traffic(args.traffic_file, kname)
+    prof = profile_fields(args.traffic_file, kname)
+    fr = roofline_fracs(flop_pt * n, k, peak, prof, res["event_step_ms"], res["ms_per_step"])
+    achieved = fr.pop("_head")
+    roofline = {"bound": "mfma", "achieved": achieved / 1e12 if achieved else None,
+                "peak": peak / 1e12, "unit": "TFLOP/s",
+                "frac": achieved / peak if achieved else None,
+                "frac_events": fr["frac_events"], "frac_rocprof": fr["frac_rocprof"],
+                "frac_headline": fr["headline"], "kernel_ms_valid": fr["kernel_ms_valid"],
+                "event_step_ms": res["event_step_ms"],
+                **({"kernel_ms_note": fr["kernel_ms_note"]} if "kernel_ms_note" in fr else {}),
+                "traffic": traffic, "kernel": kname,
+                "kernel_ms": k, "algorithmic_flop_per_point": flop_pt,
+                "points_per_launch": n, **prof}
+    diag = "ann_diag_summary.json" if mode == "fp32" else f"ann_{mode}_diag_summary.json"
+    roofline["pipes"] = load_pipe(os.path.join(args.pmc_dir, diag), kname)
+    return roofline
+
+
 def run_ann(job, args, mode="fp32"):
     import torch
     from inversekinematicsann_amd import _native
@@ -516,9 +596,10 @@ def run_ann(job, args, mode="fp32"):
     res = timed(ctx, step, args, world)
     st = ctx.stats_fetch()
     mx, sm, _, _ = _stats_over_ranks(job, st, res)
-    # the p99 from the last sharded step's gathered histograms, BEFORE the gather
-    # check's plain re-solves (a plain call ends the sharded call's state: ADVICE r04)
-    res["p99_fk_err"] = _p99(job, derr, world)
+    if args.full:
+        # the p99 from the last sharded step's gathered histograms, BEFORE the gather
+        # check's plain re-solves (a plain call ends the sharded call's state: ADVICE r04)
+        res["p99_fk_err"] = _p99(job, derr, world)
     if job.sc is not None:
         res["gather_chunks"] = job.sc.info()[2]
         res["gather_ms"] = st.gather_ms
@@ -528,40 +609,18 @@ def run_ann(job, args, mode="fp32"):
             ctx.ann_solve_device(job.dpts[b:e], a, torch.empty(e - b, dtype=torch.float64,
                                                                device="cuda"))
             return {"ang": a}
-        res["gather_check"] = gather_check(job, {"ang": dang}, resolve)
+        if args.full:
+            res["gather_check"] = gather_check(job, {"ang": dang}, resolve)
     res["max_fk_err"] = mx
     res["mean_fk_err"] = sm / job.total
     res["fk_err_note"] = ("random Glorot weights (the reference .h5 is not shipped): the FK "
                           "round trip is computed in the same launch; not model accuracy")
-    res["outputs"] = {"ang": dang}
+    # what the step's caller receives (the FK errors stay local in a sharded call)
+    res["outputs"] = {"ang": dang, **({"fk_err": derr} if job.sc is None else {})}
     if args.end_to_end:
         res["end_to_end"] = end_to_end(job, lambda hp, pinned: _host_ann(job, hp, pinned), args)
     ctx.ann_set_mode("fp32")
-    flop_pt = m.flops_per_point()
-    kname = "ann_fused_kernel" if mode == "fp32" else f"ann_fused_kernel_{mode}"
-    k = res["kernels"].get(kname)
-    n = job.n_local
-    # split modes: k bf16 / fp16 MFMA products per fp32 product, so the
-    # fp32-equivalent matrix peak is the 16-bit peak / k (the input and output
-    # layers stay fp32)
-    peak = (FP32_MFMA_PEAK if mode == "fp32" else
-            (BF16_MFMA_PEAK if mode == "bf16x6" else FP16_MFMA_PEAK) / SPLIT_PRODUCTS[mode])
-    traffic = load_traffic(args.traffic_file, kname)
-    prof = profile_fields(args.traffic_file, kname)
-    fr = roofline_fracs(flop_pt * n, k, peak, prof, res["event_step_ms"], res["ms_per_step"])
-    achieved = fr.pop("_head")
-    res["roofline"] = {"bound": "mfma", "achieved": achieved / 1e12 if achieved else None,
-                       "peak": peak / 1e12, "unit": "TFLOP/s",
-                       "frac": achieved / peak if achieved else None,
-                       "frac_events": fr["frac_events"], "frac_rocprof": fr["frac_rocprof"],
-                       "frac_headline": fr["headline"], "kernel_ms_valid": fr["kernel_ms_valid"],
-                       "event_step_ms": res["event_step_ms"],
-                       **({"kernel_ms_note": fr["kernel_ms_note"]} if "kernel_ms_note" in fr else {}),
-                       "traffic": traffic, "kernel": kname,
-                       "kernel_ms": k, "algorithmic_flop_per_point": flop_pt,
-                       "points_per_launch": n, **prof}
-    diag = "ann_diag_summary.json" if mode == "fp32" else f"ann_{mode}_diag_summary.json"
-    res["roofline"]["pipes"] = load_pipe(os.path.join(args.pmc_dir, diag), kname)
+    res["roofline"] = _ann_roofline(job, args, res, m, mode) if args.full else None
     if mode == "fp32":
         res["dtype"] = "fp32"
         res["workload"] = ("ANN MLP forward (3-12x500tanh-4, fp32) + fused FK round-trip error, "
@@ -575,6 +634,42 @@ def run_ann(job, args, mode="fp32"):
                            "(accuracy: tests/test_gpu_parity.py::test_ann_split_modes and "
                            "cpu_baseline.parity) + fused FK round-trip error, " + _batch_words(job))
     return res
+
+
+def _fabrik_roofline(job, args, res, dit, tol, max_iter):
+    """The FABRIK leg's roofline entry (--full: it needs the per-kernel timings)."""
+    # this rank's own iterations (the kernel's work), from its shard of the rows
+    local_iters = sum(int(dit[b:e].sum().item()) for b, e in _own_parts(job))
+    local_points = sum(e - b for b, e in _own_parts(job))
+    k = res["kernels"].get("fabrik_iter_kernel")
+    # SURVEY 8(d): 132 flop per iteration + 150 per point (seed and angles, both in
+    # this kernel)
+    flops = FABRIK_FLOP_PER_ITER * local_iters + FABRIK_FLOP_PER_POINT * local_points
+    pkey = "fabrik_iter_kernel" if (tol, max_iter) != (1e-5, 200) else \
+        "fabrik_tol1e-5/fabrik_iter_kernel"
+    traffic = load_traffic(args.traffic_file, pkey)
+    prof = profile_fields(args.traffic_file, pkey)
+    fr = roofline_fracs(flops, k, FP64_VALU_PEAK, prof, res["event_step_ms"], res["ms_per_step"])
+    achieved = fr.pop("_head")
+    return {"bound": "valu_fp64", "achieved": achieved / 1e12 if achieved else None,
+            "peak": FP64_VALU_PEAK / 1e12, "unit": "TFLOP/s",
+            "frac": achieved / FP64_VALU_PEAK if achieved else None,
+            "frac_events": fr["frac_events"], "frac_rocprof": fr["frac_rocprof"],
+            "frac_headline": fr["headline"], "kernel_ms_valid": fr["kernel_ms_valid"],
+            "event_step_ms": res["event_step_ms"],
+            **({"kernel_ms_note": fr["kernel_ms_note"]} if "kernel_ms_note" in fr else {}),
+            "traffic": traffic, "kernel": "fabrik_iter_kernel", "kernel_ms": k,
+            "algorithmic_flop_per_iteration": FABRIK_FLOP_PER_ITER,
+            "algorithmic_flop_per_point": FABRIK_FLOP_PER_POINT,
+            "iterations_per_launch": local_iters,
+            "points_per_launch": local_points,
+            **prof,
+            # the flop count prices a correctly rounded sqrt / division as
+            # one flop; the pipes say how busy the SIMDs actually are
+            "pipes": load_pipe(os.path.join(
+                args.pmc_dir, "fabrik_diag_summary.json" if pkey ==
+                "fabrik_iter_kernel" else "fabrik_tol1e-5_diag_summary.json"),
+                "fabrik_iter_kernel")}
 
 
 def run_fabrik(job, args, tol=None, max_iter=None):
@@ -626,23 +721,26 @@ def run_fabrik(job, args, tol=None, max_iter=None):
         table["sha16"] = hashlib.sha256(t.tobytes()).hexdigest()[:16]
         table["cells_seen"] = int((t > 0).sum())
 
-    res = timed(ctx, step, args, world, warm=warm, after_warm=after_warm)
-    res["order_table"] = table
+    res = timed(ctx, step, args, world, warm=warm, after_warm=after_warm if args.full else None)
+    if args.full:
+        res["order_table"] = table
     del wpts, wang, wit, werr
     if job.sc is not None:
         res["gather_chunks"] = job.sc.info()[2]
         res["gather_ms"] = ctx.stats_fetch().gather_ms  # the last timed step's gathers
         res["gathered_bytes_per_row"] = 32
+    if job.sc is not None and args.full:
         # untimed: the same sharded call with the iteration counts gathered too
         # (the rows are the timed steps' own: the solve is deterministic)
         solve(batch, dang, dit, derr)
         ctx.sync()
     st = ctx.stats_fetch()
     mx, sm, sum_iters, n_capped = _stats_over_ranks(job, st, res)
-    # the p99 from the last sharded call's gathered histograms, BEFORE the gather
-    # check's plain re-solves (a plain call ends the sharded call's state: ADVICE r04)
-    res["p99_fk_err"] = _p99(job, derr, world)
-    if job.sc is not None:
+    if args.full:
+        # the p99 from the last sharded call's gathered histograms, BEFORE the gather
+        # check's plain re-solves (a plain call ends the sharded call's state: ADVICE r04)
+        res["p99_fk_err"] = _p99(job, derr, world)
+    if job.sc is not None and args.full:
         def resolve(b, e):
             a = torch.empty((e - b, 4), dtype=torch.float64, device="cuda")
             i = torch.empty(e - b, dtype=torch.int32, device="cuda")
@@ -661,42 +759,16 @@ def run_fabrik(job, args, tol=None, max_iter=None):
     res["n_capped"] = int(n_capped)
     res["max_fk_err"] = mx
     res["mean_fk_err"] = sm / job.total
-    res["outputs"] = {"ang": dang, "iters": dit}
+    # what the step's caller receives (a sharded timed step gathers the angles only:
+    # the iteration counts come from --full's untimed call, the FK errors stay local)
+    res["outputs"] = {"ang": dang,
+                      **({"iters": dit} if job.sc is None or args.full else {}),
+                      **({"fk_err": derr} if job.sc is None else {})}
     if args.end_to_end:
         res["end_to_end"] = end_to_end(
             job, lambda hp, pinned: _host_fabrik(job, hp, pinned, tol, max_iter), args)
-    # this rank's own iterations (the kernel's work), from its shard of the rows
-    local_iters = sum(int(dit[b:e].sum().item()) for b, e in _own_parts(job))
-    local_points = sum(e - b for b, e in _own_parts(job))
-    k = res["kernels"].get("fabrik_iter_kernel")
-    # 132 flop per iteration + 150 per point (seed and angles, both in
-    # this kernel)
-    flops = FABRIK_FLOP_PER_ITER * local_iters + FABRIK_FLOP_PER_POINT * local_points
-    pkey = "fabrik_iter_kernel" if (tol, max_iter) != (1e-5, 200) else \
-        "fabrik_tol1e-5/fabrik_iter_kernel"
-    traffic = load_traffic(args.traffic_file, pkey)
-    prof = profile_fields(args.traffic_file, pkey)
-    fr = roofline_fracs(flops, k, FP64_VALU_PEAK, prof, res["event_step_ms"], res["ms_per_step"])
-    achieved = fr.pop("_head")
-    res["roofline"] = {"bound": "valu_fp64", "achieved": achieved / 1e12 if achieved else None,
-                       "peak": FP64_VALU_PEAK / 1e12, "unit": "TFLOP/s",
-                       "frac": achieved / FP64_VALU_PEAK if achieved else None,
-                       "frac_events": fr["frac_events"], "frac_rocprof": fr["frac_rocprof"],
-                       "frac_headline": fr["headline"], "kernel_ms_valid": fr["kernel_ms_valid"],
-                       "event_step_ms": res["event_step_ms"],
-                       **({"kernel_ms_note": fr["kernel_ms_note"]} if "kernel_ms_note" in fr else {}),
-                       "traffic": traffic, "kernel": "fabrik_iter_kernel", "kernel_ms": k,
-                       "algorithmic_flop_per_iteration": FABRIK_FLOP_PER_ITER,
-                       "algorithmic_flop_per_point": FABRIK_FLOP_PER_POINT,
-                       "iterations_per_launch": local_iters,
-                       "points_per_launch": local_points,
-                       **prof,
-                       # the flop count prices a correctly rounded sqrt / division as
-                       # one flop; the pipes say how busy the SIMDs actually are
-                       "pipes": load_pipe(os.path.join(
-                           args.pmc_dir, "fabrik_diag_summary.json" if pkey ==
-                           "fabrik_iter_kernel" else "fabrik_tol1e-5_diag_summary.json"),
-                           "fabrik_iter_kernel")}
+    res["roofline"] = (_fabrik_roofline(job, args, res, dit, tol, max_iter) if args.full
+                       else None)
     res["dtype"] = "f64"
     res["workload"] = (f"FABRIK ikine (seed FK + loop + angles) + fused FK round-trip error, "
                        f"tol {tol:g} / {max_iter} iterations, float64, " + _batch_words(job))
@@ -751,6 +823,8 @@ def run_fk(job, args):
                        "kernel": "fk_kernel", "kernel_ms": k,
                        "algorithmic_bytes_per_point": FK_BYTES_PER_POINT,
                        "points_per_launch": n}
+    if not args.full:  # (no per-kernel timings to price)
+        res["roofline"] = None
     res["dtype"] = "f64"
     res["unit"] = "FK evaluations/s"
     res["workload"] = f"FK (DH chain, float64), {_pts(n)} angle vectors per GPU"
@@ -765,9 +839,9 @@ def warm_batch(n):
 
 
 def timed(ctx, step, args, world, warm=None, after_warm=None):
-    """W warm-up steps, one step timed per kernel, then K steps between barriers.
-    Every wait on the steps is ctx.sync() first (ik_ctx_sync): bounded by the
-    communicator's deadline at N > 1, so a stuck peer ends the run with
+    """W warm-up steps, with --full the steps timed per kernel, then K steps
+    between barriers.  Every wait on the steps is ctx.sync() first (ik_ctx_sync):
+    bounded by the communicator's deadline at N > 1, so a stuck peer ends the run with
     IK_E_RCCL rather than hanging it; torch.cuda.synchronize() then returns at once."""
     import torch
     for _ in range(args.warmup):
@@ -776,62 +850,63 @@ def timed(ctx, step, args, world, warm=None, after_warm=None):
     torch.cuda.synchronize()
     if after_warm is not None:
         after_warm()
-    # per-kernel durations: the library launches each kernel of a timed call with
-    # hipExtLaunchKernel's start / stop events, which the dispatch itself stamps
-    # (ik_ctx_set_timing), so a kernel's interval holds neither the
-    # kernels ahead of it in the step nor the host's launch latency.  TIMING_LEAD +
-    # TIMING_REPS steps back to back with the timings accumulating (set_timing(2):
-    # no host sync between them, so no step starts from an idle, clocked-down GPU --
-    # a 0.4 ms FK step behind a single lead step still ran ~5 % slow); the median
-    # of the last TIMING_REPS steps' per-kernel sums, each step's own duration from
-    # the stream's events around it.
     kernels, event_step_ms = {}, None
-    nsteps = TIMING_LEAD + TIMING_REPS
-    ctx.set_timing(2)
-    evs = []
-    for _ in range(nsteps):
-        s0 = torch.cuda.Event(enable_timing=True)
-        s1 = torch.cuda.Event(enable_timing=True)
-        s0.record()
-        step()
-        s1.record()
-        evs.append((s0, s1))
-    ctx.sync()
-    torch.cuda.synchronize()
-    times = ctx.kernel_times()
-    ctx.set_timing(False)
-    if times and len(times) % nsteps == 0 and len(times) < 64:
-        per_step = len(times) // nsteps
-        per = {}
-        for s_ in range(TIMING_LEAD, nsteps):
-            one = {}
-            for name, ms in times[s_ * per_step:(s_ + 1) * per_step]:
-                one[name] = one.get(name, 0.0) + ms
-            for name, ms in one.items():
-                per.setdefault(name, []).append(ms)
-        kernels = {name: float(np.median(v)) for name, v in per.items()}
-        event_step_ms = float(np.median([a.elapsed_time(b) for a, b in evs[TIMING_LEAD:]]))
-    else:  # (more kernels a step than the 64 slots hold: each step timed on its own)
-        per, steps_ms = {}, []
-        for _ in range(TIMING_REPS):
-            step()
-            ctx.set_timing(True)
+    if args.full:
+        # per-kernel durations: the library launches each kernel of a timed call with
+        # hipExtLaunchKernel's start / stop events, which the dispatch itself stamps
+        # (ik_ctx_set_timing), so a kernel's interval holds neither the
+        # kernels ahead of it in the step nor the host's launch latency.  TIMING_LEAD +
+        # TIMING_REPS steps back to back with the timings accumulating (set_timing(2):
+        # no host sync between them, so no step starts from an idle, clocked-down GPU --
+        # a 0.4 ms FK step behind a single lead step still ran ~5 % slow); the median
+        # of the last TIMING_REPS steps' per-kernel sums, each step's own duration from
+        # the stream's events around it.
+        nsteps = TIMING_LEAD + TIMING_REPS
+        ctx.set_timing(2)
+        evs = []
+        for _ in range(nsteps):
             s0 = torch.cuda.Event(enable_timing=True)
             s1 = torch.cuda.Event(enable_timing=True)
             s0.record()
             step()
             s1.record()
-            ctx.sync()
-            torch.cuda.synchronize()
-            steps_ms.append(s0.elapsed_time(s1))
-            one = {}
-            for name, ms in ctx.kernel_times():
-                one[name] = one.get(name, 0.0) + ms
-            ctx.set_timing(False)
-            for name, ms in one.items():
-                per.setdefault(name, []).append(ms)
-        kernels = {name: float(np.median(v)) for name, v in per.items()}
-        event_step_ms = float(np.median(steps_ms))
+            evs.append((s0, s1))
+        ctx.sync()
+        torch.cuda.synchronize()
+        times = ctx.kernel_times()
+        ctx.set_timing(False)
+        if times and len(times) % nsteps == 0 and len(times) < 64:
+            per_step = len(times) // nsteps
+            per = {}
+            for s_ in range(TIMING_LEAD, nsteps):
+                one = {}
+                for name, ms in times[s_ * per_step:(s_ + 1) * per_step]:
+                    one[name] = one.get(name, 0.0) + ms
+                for name, ms in one.items():
+                    per.setdefault(name, []).append(ms)
+            kernels = {name: float(np.median(v)) for name, v in per.items()}
+            event_step_ms = float(np.median([a.elapsed_time(b) for a, b in evs[TIMING_LEAD:]]))
+        else:  # (more kernels a step than the 64 slots hold: each step timed on its own)
+            per, steps_ms = {}, []
+            for _ in range(TIMING_REPS):
+                step()
+                ctx.set_timing(True)
+                s0 = torch.cuda.Event(enable_timing=True)
+                s1 = torch.cuda.Event(enable_timing=True)
+                s0.record()
+                step()
+                s1.record()
+                ctx.sync()
+                torch.cuda.synchronize()
+                steps_ms.append(s0.elapsed_time(s1))
+                one = {}
+                for name, ms in ctx.kernel_times():
+                    one[name] = one.get(name, 0.0) + ms
+                ctx.set_timing(False)
+                for name, ms in one.items():
+                    per.setdefault(name, []).append(ms)
+            kernels = {name: float(np.median(v)) for name, v in per.items()}
+            event_step_ms = float(np.median(steps_ms))
     torch.cuda.synchronize()
     barrier(world)
     torch.cuda.synchronize()
@@ -1216,7 +1291,7 @@ def strong_job(ctx, sc, world, rank, total):
 
 
 def main():
-    args = parse()
+    args = plain(parse())
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         # a line labelled with one GPU count must measure that many ranks
@@ -1259,6 +1334,8 @@ def main():
         runners[f"ann_{om}"] = (lambda mm: lambda j, a: run_ann(j, a, mode=mm))(om)
     res = runners[args.method](job, args)
     outputs = {args.method: res["outputs"]}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res["outputs"])
     checks = {args.method: res.get("gather_check")}
     secondary = {}
     if args.secondary and args.method != "fk":

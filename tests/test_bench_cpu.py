@@ -319,3 +319,43 @@ def test_rocprof_median_over_boxes():
     pf = bench.profile_fields(lb, "fabrik_iter_kernel")
     assert pf["rocprof_avg_ms"] == json.load(open(lb))["fabrik_iter_kernel"]["rocprof_avg_ms"]
     assert "rocprof_boxes_ms" not in pf
+
+
+def test_plain_run_switches_the_other_legs_off():
+    """Without --full only the headline is measured, whatever the legs' own options
+    say; with it they keep their values."""
+    import bench
+    a = bench.plain(bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3",
+                                 "--end-to-end", "1", "--cpu-seconds", "5"]))
+    assert not a.full and (a.steps, a.warmup) == (7, 3) and a.dump_outputs is None
+    assert (a.secondary, a.end_to_end, a.cold, a.strong_legs, a.cpu_seconds) == (0, 0, 0, 0, 0.0)
+    a = bench.plain(bench.parse(["--full", "--cold", "0", "--dump-outputs", "d"]))
+    assert a.full and a.dump_outputs == "d"
+    assert (a.secondary, a.end_to_end, a.cold, a.strong_legs, a.cpu_seconds) == (1, 1, 0, 1, 10.0)
+
+
+def test_dump_outputs_dtypes_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 stays, the rest becomes float64; arrays over the
+    limit are cut to one seeded sample of rows, the same from call to call."""
+    import torch
+    import bench
+    n = 1000
+    out = {"ang": torch.arange(n * 4, dtype=torch.float32).reshape(n, 4),
+           "iters": torch.arange(n, dtype=torch.int32),
+           "fk_err": torch.arange(n, dtype=torch.float64) / 7}
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in out}
+    assert got["ang"].dtype == np.float32 and got["iters"].dtype == np.float64
+    assert got["fk_err"].dtype == np.float64
+    for k, v in out.items():
+        assert got[k].shape == tuple(v.shape) and np.array_equal(got[k], v.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 32 * 100)  # 32 B a row here: 100 rows
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    bench.dump_outputs(str(tmp_path / "c"), out)
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in out}
+    rows = b["iters"].astype(np.int64)
+    assert rows.shape == (100,) and (np.diff(rows) > 0).all()
+    assert sum(v.nbytes for v in b.values()) <= 32 * 100
+    for k, v in out.items():
+        assert np.array_equal(b[k], v.numpy()[rows])
+        assert np.array_equal(b[k], np.load(tmp_path / "c" / f"{k}.npy"))

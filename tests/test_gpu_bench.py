@@ -26,7 +26,7 @@ def _bench_worker(q):
         n = 20_000
         pts = random_dist(n, seed=0)
         job = bench.Job(ctx, sc, pts, torch.from_numpy(pts).cuda(), 0, n, 1)
-        args = bench.parse(["--steps", "2", "--warmup", "1", "--end-to-end", "0",
+        args = bench.parse(["--full", "--steps", "2", "--warmup", "1", "--end-to-end", "0",
                             "--cpu-seconds", "0"])
         out = {}
         r = bench.run_ann(job, args)
@@ -37,8 +37,8 @@ def _bench_worker(q):
                          r.get("gathered_bytes_per_row"), "cold" in r)
         # the strong legs' machinery on a small batch
         sjob = bench.strong_job(ctx, sc, 1, 0, 30_000)
-        sargs = bench.parse(["--steps", "2", "--warmup", "1", "--end-to-end", "0", "--cold", "0",
-                             "--cpu-seconds", "0"])
+        sargs = bench.parse(["--full", "--steps", "2", "--warmup", "1", "--end-to-end", "0",
+                             "--cold", "0", "--cpu-seconds", "0"])
         for key, fn in bench.strong_legs().items():
             r = fn(sjob, sargs)
             e = bench.secondary_entry(key, r, 30_000, 1, sargs)
@@ -115,3 +115,47 @@ def test_automatic_chunks_one_for_both_methods():
     res = _spawn(_auto_chunks_worker, timeout=120)
     assert res == {"fabrik_g1": 1, "ann_g1": 1, "fabrik_g2": 1, "ann_g2": 1,
                    "fabrik_g8": 1, "ann_g8": 1}, res
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run: the contract's fields, --steps timed steps, none of
+    --full's legs, and --dump-outputs writes the last step's angles and FK errors
+    (here checked against a solve of the same batch)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    import torch
+    import bench
+    from inversekinematicsann_amd import _native
+    from inversekinematicsann_amd.kinematics.ann import (REFERENCE_X_SCALER as XS,
+                                                         REFERENCE_Y_SCALER as YS, glorot_model)
+    from inversekinematicsann_amd.robot.position_generator import random_dist
+    n = 3001
+    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(bench.__file__), "bench.py"),
+                        "--gpus", "1", "--steps", "3", "--warmup", "1", "--points", str(n),
+                        "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == bench.METRIC and d["unit"] == "IK solutions/s" and d["dtype"] == "fp32"
+    assert d["higher_is_better"] is True and d["steps"] == 3 and d["warmup"] == 1
+    assert d["ms_per_step"] > 0 and abs(d["value"] - n / (d["ms_per_step"] / 1e3)) <= 1e-6 * d["value"]
+    for k in ("secondary", "cpu_baseline", "end_to_end", "p99_fk_err"):
+        assert k not in d
+    assert d["roofline"] is None and d["kernels_ms"] == {}
+    assert sorted(os.listdir(tmp_path)) == ["ang.npy", "fk_err.npy"]
+    ang, err = np.load(tmp_path / "ang.npy"), np.load(tmp_path / "fk_err.npy")
+    assert ang.dtype == np.float32 and ang.shape == (n, 4)
+    assert err.dtype == np.float64 and err.shape == (n,)
+    ctx = _native.Context(0)
+    m = glorot_model(bench.ANN_DIMS, seed=0)
+    ctx.ann_load(m.weights, m.biases, m.activations, XS.mean, XS.scale, YS.mean, YS.scale)
+    ref = torch.empty((n, 4), dtype=torch.float32, device="cuda")
+    ref_err = torch.empty(n, dtype=torch.float64, device="cuda")
+    ctx.ann_solve_device(torch.from_numpy(random_dist(n, seed=0)).cuda(), ref, ref_err)
+    assert np.array_equal(ang, ref.cpu().numpy()) and np.array_equal(err, ref_err.cpu().numpy())
+    assert abs(d["max_fk_err"] - err.max()) <= 1e-12 * err.max()

@@ -14,7 +14,7 @@ TOL=${TOL:-1e-3}
 MI=${MI:-100}
 for i in $(seq 1 $P); do
   timeout -s KILL 120 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv \
-      -d $OUT/p$i -- python bench.py --method fabrik --tol $TOL --max-iter $MI --secondary 0 \
+      -d $OUT/p$i -- python bench.py --full --method fabrik --tol $TOL --max-iter $MI --secondary 0 \
       --cpu-seconds 0 --end-to-end 0 --cold 0 --steps 20 --warmup 5 > $OUT/p$i.json 2> $OUT/p$i.err
   rc=$?
   echo "p$i rc=$rc"

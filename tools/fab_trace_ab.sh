@@ -16,7 +16,7 @@ for r in $(seq 1 $REPS); do
     if [ "$spec" != "$lib" ]; then envs=$(echo "${spec#*:}" | tr ',' ' '); fi
     tag=$(echo "${spec%.so*}${spec#*.so}" | tr -c 'a-zA-Z0-9_\n' '_')_${TOL}_$r
     env $envs IKHIP_LIB=$PWD/inversekinematicsann_amd/$lib timeout -s KILL 120 rocprofv3 --kernel-trace \
-        --output-format csv -d $OUT/$tag -- python bench.py --method fabrik --tol $TOL \
+        --output-format csv -d $OUT/$tag -- python bench.py --full --method fabrik --tol $TOL \
         --max-iter $MI --secondary 0 --cpu-seconds 0 --end-to-end 0 --cold 0 --steps 30 \
         --warmup 5 > $OUT/$tag.json 2> $OUT/$tag.err
     rc=$?

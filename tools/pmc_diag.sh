@@ -2,6 +2,7 @@
 # one counter group per pass.
 set -o pipefail
 cd $GRAFT_REPO_ROOT
+export OUT=${OUT:-bench_out}
 export TMPDIR=/tmp
 m=${1:-ann}
 case $m in
@@ -17,9 +18,9 @@ for grp in "GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES" \
            "SQ_ACTIVE_INST_VALU SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64" \
            "TCC_REQ_sum TCC_READ_sum TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum"; do
   i=$((i+1))
-  timeout -s KILL 150 rocprofv3 --pmc $grp --output-format csv -d gpurun_out/pmc_${m}_$i -- python bench.py $BARGS --steps 1 --warmup 1 --cpu-seconds 0 --secondary 0 --end-to-end 0 > gpurun_out/pmc_${m}_$i.log 2>&1
+  timeout -s KILL 150 rocprofv3 --pmc $grp --output-format csv -d $OUT/pmc_${m}_$i -- python bench.py --full $BARGS --steps 1 --warmup 1 --cpu-seconds 0 --secondary 0 --end-to-end 0 > $OUT/pmc_${m}_$i.log 2>&1
   rc=$?
   echo "pmc $m $i rc=$rc"
   if [ $rc -ne 0 ]; then exit $rc; fi
 done
-python tools/pmc_summary.py gpurun_out/pmc_${m}_* > gpurun_out/pmc_${m}_summary.json
+python tools/pmc_summary.py $OUT/pmc_${m}_* > $OUT/pmc_${m}_summary.json

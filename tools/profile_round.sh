@@ -20,9 +20,9 @@ step() {  # step <name> <timeout> <cmd...>: stops the script on crash / timeout
 }
 STEPS=${STEPS:-20}
 WARM=${WARM:-5}
-step bench_default 300 python bench.py --gpus 1 --steps $STEPS --warmup $WARM
+step bench_default 300 python bench.py --full --gpus 1 --steps $STEPS --warmup $WARM
 BENCH="--gpus 1 --cpu-seconds 0 --end-to-end 0 --cold 0"
-step trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python bench.py $BENCH --steps $STEPS --warmup $WARM
+step trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python bench.py --full $BENCH --steps $STEPS --warmup $WARM
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" \
            "GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES" \
@@ -30,7 +30,7 @@ for grp in "FETCH_SIZE" "WRITE_SIZE" \
            "TCC_HIT_sum TCC_MISS_sum" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY"; do
   i=$((i+1))
-  step pmc_$i 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/pmc_$i -- python bench.py $BENCH --steps 5 --warmup $WARM
+  step pmc_$i 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/pmc_$i -- python bench.py --full $BENCH --steps 5 --warmup $WARM
 done
 python tools/profile_summary.py --dir $OUT --steps $STEPS --warmup $WARM --pmc-steps 5 --out $OUT/summary > $OUT/summary.log 2>&1
 cat $OUT/steps.txt
