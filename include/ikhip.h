@@ -196,6 +196,43 @@ int ik_ann_get_mode(ik_ctx *ctx); /* the mode, or -ik_status */
  * device), or IK_ANN_BF16X6 for IK_ANN_FP16X3 on the layered path. */
 int ik_ann_effective_mode(ik_ctx *ctx);
 
+/* ---- ANN training ----------------------------------------------------------
+ * ANN.train_model, kinematics/ann.py:27-68: Keras' fit of a Dense stack with
+ * loss 'mse' and Adam, one batch per step.  The training state (fp32 master
+ * weights W[l] [dims[l]][dims[l+1]] row-major as in ik_ann_load, the Adam moments,
+ * the batch's activations) is apart from the loaded inference model; a context
+ * may hold both.  n_layers 1..24, every dims[l] 1..1024 (dims[0] and
+ * dims[n_layers] are free here), max_batch 1..4096.  The loss of a batch is
+ * sum((A_L - y)^2) / (rows dims[n_layers]), accumulated in float64; all GEMMs are
+ * exact fp32 (v_mfma_f32_32x32x2_f32) with the inference kernels' activations,
+ * and no reduction depends on timing: the same state and batches give the same
+ * bits.  Adam is Keras': m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2,
+ * W -= lr sqrt(1 - b2^t) / (1 - b1^t) m / (sqrt(v) + eps).  All pointers are HOST
+ * pointers and every call blocks.  IK_E_BADARG: calls out of order, rows above
+ * max_batch, a perm entry outside 0..n_train-1. */
+int ik_ann_train_begin(ik_ctx *ctx, int n_layers, const int32_t *dims, const int32_t *acts,
+                       const float *const *W, const float *const *b, int max_batch, double lr,
+                       double beta1, double beta2, double eps);
+/* The data set, already scaled: x n_train x dims[0], y n_train x dims[n_layers], and
+ * the validation rows (n_val may be 0). */
+int ik_ann_train_data(ik_ctx *ctx, const float *x, const float *y, int64_t n_train,
+                      const float *xv, const float *yv, int64_t n_val);
+/* The gradients of one batch's loss (dW[l], db[l] as W[l], b[l]); no update. */
+int ik_ann_train_grads(ik_ctx *ctx, const float *x, const float *y, int rows, float *const *dW,
+                       float *const *db, double *loss);
+/* One Adam step on one batch; loss is the batch's loss before the update. */
+int ik_ann_train_step(ik_ctx *ctx, const float *x, const float *y, int rows, double *loss);
+/* One epoch over the data set in the order perm (n_train entries; NULL = data
+ * order): ceil(n_train / batch) steps, the last one short.  train_loss is the
+ * mean of the steps' losses weighted by their rows (Keras' running mean),
+ * val_loss the loss of the end-of-epoch weights over the validation rows (NaN
+ * without any). */
+int ik_ann_train_epoch(ik_ctx *ctx, const int32_t *perm, int batch, double *train_loss,
+                       double *val_loss);
+/* Copies out what = 0 the weights and biases, 1 Adam's m, 2 Adam's v. */
+int ik_ann_train_get(ik_ctx *ctx, int what, float *const *W, float *const *b);
+int ik_ann_train_end(ik_ctx *ctx);
+
 /* Per-kernel timing with HIP events: when on, every kernel a call launches
  * goes through hipExtLaunchKernel with a start and a stop event, which the
  * dispatch itself stamps (the kernel's own start and end: not the kernels ahead

@@ -42,7 +42,10 @@ EXPORTED_SYMBOLS = ("ik_ctx_create", "ik_ctx_destroy", "ik_ctx_set_stream", "ik_
                     "ik_tail_reduce", "ik_fkhist_bin", "ik_fkhist_upper", "ik_fk_err_quantile",
                     "ik_ann_solve_sharded", "ik_fabrik_solve_sharded", "ik_host_alloc",
                     "ik_host_free", "ik_ctx_sync", "ik_comm_set_timeout",
-                    "ik_comm_loopback_stall", "ik_fabrik_order_get", "ik_fabrik_order_set")
+                    "ik_comm_loopback_stall", "ik_fabrik_order_get", "ik_fabrik_order_set",
+                    "ik_ann_train_begin", "ik_ann_train_data", "ik_ann_train_grads",
+                    "ik_ann_train_step", "ik_ann_train_epoch", "ik_ann_train_get",
+                    "ik_ann_train_end")
 ANN_MODES = {"fp32": 0, "bf16x6": 1, "fp16x3": 2}
 
 
@@ -163,6 +166,17 @@ def load_library(path: str = LIB_PATH):
         L.ik_ann_solve_sharded.argtypes = [vp, dp, i64, dp, dp, ctypes.c_int, st]
         L.ik_fabrik_solve_sharded.argtypes = [vp, dp, i64, ctypes.c_double, i32, dp, ip, dp,
                                               ctypes.c_int, st]
+        pp = ctypes.POINTER(ctypes.c_void_p)
+        pd = ctypes.POINTER(ctypes.c_double)
+        L.ik_ann_train_begin.argtypes = [vp, ctypes.c_int, ip, ip, pp, pp, ctypes.c_int,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_double]
+        L.ik_ann_train_data.argtypes = [vp, dp, dp, i64, dp, dp, i64]
+        L.ik_ann_train_grads.argtypes = [vp, dp, dp, ctypes.c_int, pp, pp, pd]
+        L.ik_ann_train_step.argtypes = [vp, dp, dp, ctypes.c_int, pd]
+        L.ik_ann_train_epoch.argtypes = [vp, ip, ctypes.c_int, pd, pd]
+        L.ik_ann_train_get.argtypes = [vp, ctypes.c_int, pp, pp]
+        L.ik_ann_train_end.argtypes = [vp]
         _lib = L
         return L
 
@@ -473,6 +487,97 @@ class Context:
         self._on_torch_stream(lambda: self._check(self.lib.ik_ann_solve(
             self.handle, args[0], n, args[1], args[2], flags, ctypes.byref(s))))
         return s
+
+    # -- training (include/ikhip.h "ANN training") ---------------------------
+    def train_begin(self, weights: Sequence, biases: Sequence, acts: Sequence[str],
+                    max_batch: int = 32, lr: float = 1e-5, beta1: float = 0.9,
+                    beta2: float = 0.999, eps: float = 1e-7):
+        """ik_ann_train_begin: upload the initial weights; Keras' Adam defaults."""
+        Ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
+        bs = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in biases]
+        nl = len(Ws)
+        dims = [Ws[0].shape[0]] + [w.shape[1] for w in Ws]
+        for l in range(nl):
+            if Ws[l].shape != (dims[l], dims[l + 1]) or bs[l].shape != (dims[l + 1],):
+                raise ValueError(f"layer {l}: kernel {Ws[l].shape} / bias {bs[l].shape} mismatch")
+        dims_a = np.array(dims, np.int32)
+        acts_a = np.array([ACTS[a] for a in acts], np.int32)
+        wp = (ctypes.c_void_p * nl)(*[w.ctypes.data for w in Ws])
+        bp = (ctypes.c_void_p * nl)(*[b.ctypes.data for b in bs])
+        self._check(self.lib.ik_ann_train_begin(self.handle, nl, _ptr(dims_a), _ptr(acts_a), wp,
+                                                bp, int(max_batch), float(lr), float(beta1),
+                                                float(beta2), float(eps)))
+        self._train_dims = dims
+
+    def _train_xy(self, x, y):
+        d = getattr(self, "_train_dims", None)
+        if d is None:  # the library reports the order of calls
+            return _host(x, np.float32), _host(y, np.float32)
+        xa, ya = _host(x, np.float32, d[0]), _host(y, np.float32, d[-1])
+        if xa.shape[0] != ya.shape[0]:
+            raise ValueError(f"x has {xa.shape[0]} rows, y {ya.shape[0]}")
+        return xa, ya
+
+    def _train_out(self):
+        d = self._train_dims
+        Ws = [np.empty((d[l], d[l + 1]), np.float32) for l in range(len(d) - 1)]
+        bs = [np.empty(d[l + 1], np.float32) for l in range(len(d) - 1)]
+        wp = (ctypes.c_void_p * len(Ws))(*[w.ctypes.data for w in Ws])
+        bp = (ctypes.c_void_p * len(bs))(*[b.ctypes.data for b in bs])
+        return Ws, bs, wp, bp
+
+    def train_data(self, x, y, xv=None, yv=None):
+        """ik_ann_train_data: the scaled training rows and (optionally) validation rows."""
+        xa, ya = self._train_xy(x, y)
+        if xv is None or len(xv) == 0:
+            xva = yva = None
+            nv = 0
+        else:
+            xva, yva = self._train_xy(xv, yv)
+            nv = xva.shape[0]
+        self._check(self.lib.ik_ann_train_data(self.handle, _ptr(xa), _ptr(ya), xa.shape[0],
+                                               _ptr(xva), _ptr(yva), nv))
+
+    def train_grads(self, x, y):
+        """ik_ann_train_grads: (dW list, db list, loss) of one batch; no update."""
+        xa, ya = self._train_xy(x, y)
+        loss = ctypes.c_double()
+        if getattr(self, "_train_dims", None) is None:
+            self._check(self.lib.ik_ann_train_grads(self.handle, _ptr(xa), _ptr(ya),
+                                                    xa.shape[0], None, None, ctypes.byref(loss)))
+        Ws, bs, wp, bp = self._train_out()
+        self._check(self.lib.ik_ann_train_grads(self.handle, _ptr(xa), _ptr(ya), xa.shape[0], wp,
+                                                bp, ctypes.byref(loss)))
+        return Ws, bs, loss.value
+
+    def train_step(self, x, y) -> float:
+        """ik_ann_train_step: one Adam step; returns the batch's loss before it."""
+        xa, ya = self._train_xy(x, y)
+        loss = ctypes.c_double()
+        self._check(self.lib.ik_ann_train_step(self.handle, _ptr(xa), _ptr(ya), xa.shape[0],
+                                               ctypes.byref(loss)))
+        return loss.value
+
+    def train_epoch(self, perm=None, batch: int = 32):
+        """ik_ann_train_epoch: (train_loss, val_loss) of one epoch in the order perm."""
+        p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32).reshape(-1)
+        tl, vl = ctypes.c_double(), ctypes.c_double()
+        self._check(self.lib.ik_ann_train_epoch(self.handle, _ptr(p), int(batch),
+                                                ctypes.byref(tl), ctypes.byref(vl)))
+        return tl.value, vl.value
+
+    def train_get(self, what: str = "weights"):
+        """ik_ann_train_get: (W list, b list) of "weights", Adam's "m" or "v"."""
+        code = {"weights": 0, "m": 1, "v": 2}[what]
+        if getattr(self, "_train_dims", None) is None:
+            self._check(self.lib.ik_ann_train_get(self.handle, code, None, None))
+        Ws, bs, wp, bp = self._train_out()
+        self._check(self.lib.ik_ann_train_get(self.handle, code, wp, bp))
+        return Ws, bs
+
+    def train_end(self):
+        self._check(self.lib.ik_ann_train_end(self.handle))
+        self._train_dims = None
 
     # -- multi-GPU (RCCL over xGMI; include/ikhip.h "multi-GPU") -------------
     def comm_init(self, nranks: int, rank: int, uid: bytes):

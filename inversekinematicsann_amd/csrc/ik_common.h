@@ -619,4 +619,52 @@ int64_t ann_big_rows(const AnnBigModel &m, size_t act_bytes);
 void launch_ann_big(const AnnBigModel &m, const RobotDev &r, const double *pts, int64_t n,
                     float *ang, double *fk_err, bool check_limits, DevStats *S, hipStream_t st,
                     float *act, int64_t chunk_rows, int xmode = 0);
+
+// Training (ik_train.hip): ANN.train_model's Keras fit (kinematics/ann.py:27-68)
+// as plain stream launches -- per step one forward GEMM per layer, one loss
+// kernel, one data-gradient GEMM per layer after the first, and per layer one
+// weight-gradient GEMM (the bias gradient its last row) with the Adam update in its
+// epilogue.
+// Master weights, moments and gradients are fp32 row-major [in][out] (the Keras
+// kernel layout), unpadded; every activation row is dims[l] floats.
+constexpr int kTrainMaxLayers = 24;
+constexpr int kTrainMaxWidth = 1024;
+constexpr int kTrainMaxBatch = 4096;
+struct TrainDev {
+  int n_layers = 0, max_batch = 0;
+  int dims[kTrainMaxLayers + 1] = {};
+  int act[kTrainMaxLayers] = {};
+  float *W[kTrainMaxLayers] = {}, *b[kTrainMaxLayers] = {};
+  float *mW[kTrainMaxLayers] = {}, *mb[kTrainMaxLayers] = {};  // Adam first moments
+  float *vW[kTrainMaxLayers] = {}, *vb[kTrainMaxLayers] = {};  // Adam second moments
+  float *gW[kTrainMaxLayers] = {}, *gb[kTrainMaxLayers] = {};  // gradients (ik_ann_train_grads)
+  float *A[kTrainMaxLayers + 1] = {};  // A[0]: staged inputs; A[l]: layer l's outputs of the batch
+  float *y = nullptr;                  // staged targets
+  float *dZ[2] = {};                   // max_batch x widest layer, alternating
+  double *loss = nullptr;              // loss-sum slots (one per step / validation chunk)
+  int64_t loss_slots = 0;
+  void *block = nullptr;               // the allocation the pointers above the slots point into
+  double lr = 0, beta1 = 0, beta2 = 0, eps = 0;
+  int64_t t = 0;                       // Adam steps taken
+  // the data set (ik_ann_train_data): scaled fp32 rows, and their permuted copies
+  float *X = nullptr, *Y = nullptr, *Xs = nullptr, *Ys = nullptr, *Xv = nullptr, *Yv = nullptr;
+  int32_t *perm = nullptr;
+  int64_t n_train = 0, n_val = 0;
+  void *data_block = nullptr;
+};
+struct AdamDev {
+  double b1, omb1, b2, omb2;  // beta, 1 - beta
+  float eps, alpha;           // epsilon, alpha_t
+};
+// A_l = act(A_{l-1} W_l + b_l) for every layer; x: rows x dims[0] device floats.
+void train_forward(const TrainDev &T, const float *x, int rows, hipStream_t st);
+// *slot = sum((A_L - y)^2) in float64; with want_dz, dZ[0] = 2 (A_L - y) / (rows n_out) * act'(A_L).
+void train_loss(const TrainDev &T, const float *y, int rows, double *slot, bool want_dz,
+                hipStream_t st);
+// The backward pass from dZ[0]: with adam, W / b / m / v are updated in the weight-
+// gradient kernels' epilogues; without, the gradients go to gW / gb.
+void train_backward(const TrainDev &T, const float *x, int rows, bool adam, const AdamDev &ad,
+                    hipStream_t st);
+// Xs[i] = X[perm[i]], Ys[i] = Y[perm[i]] over the training rows.
+void train_gather(const TrainDev &T, hipStream_t st);
 }  // namespace ikhip

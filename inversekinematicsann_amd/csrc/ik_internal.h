@@ -113,6 +113,8 @@ struct ik_ctx {
   ikhip::AnnBigModel ann_bigm;  // its layers (pointers into ann_buf)
   void *ann_act = nullptr;      // its activation buffers, grow-only
   size_t ann_act_bytes = 0;
+  // training state (ik_ann_train_begin .. ik_ann_train_end), apart from the loaded model
+  ikhip::TrainDev *train = nullptr;
   int fabrik_variant = 1;
   int fabrik_bpc = 0;   // IKHIP_FABRIK_BPC: iteration-kernel blocks per CU (0 = size rule)
   int fabrik_core = 2;  // IKHIP_FABRIK_CORE: 2 core + reuse, 1 sqrt_core / div_core, 0 general

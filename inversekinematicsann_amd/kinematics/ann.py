@@ -12,7 +12,11 @@ Model files (ann.py:78-95):
     models/hdf5_write.py, the scalers as joblib-dumped sklearn StandardScalers)
     so the reference's load_model can open it; `<name>.npz` (weights,
     activations and scalers) is also read.
-Training (ann.py:27-68) is out of scope for this engine.
+Training (ann.py:27-68): ANN.fit() runs the reference's recipe -- 67/33 split,
+StandardScalers fitted on the training part, Adam on MSE in batches of 32 with
+per-epoch shuffling, early stopping on val_loss -- with the forward, backward and
+Adam kernels of libikhip (ik_train.hip); the split, the scalers and the
+early-stopping loop are kinematics/train.py.  train_model() itself still raises.
 """
 from __future__ import annotations
 
@@ -124,6 +128,66 @@ class ANN:
         raise NotImplementedError("ANN training (kinematics/ann.py:27-68) is not part of the "
                                   "MI355X inference engine; train with the reference and load "
                                   "the saved .h5 with load_model()")
+
+    def fit(self, epochs, samples, features, *, batch_size=32, learning_rate=1e-5, patience=12,
+            hidden=(12, 500, "tanh"), seed=0, test_size=0.33, split_seed=42,
+            verbose=False) -> dict:
+        """Train the network on the GPU as the reference's train_model does
+        (ann.py:27-68): train_test_split(test_size, random_state=split_seed),
+        StandardScalers fitted on the training part (data cast to float32 after
+        scaling), Input(d) -> hidden Dense layers -> Dense(n_out) from
+        glorot_model(seed=seed), Adam(learning_rate) on MSE in batches of batch_size
+        (the last one short), each epoch's order a permutation from
+        np.random.default_rng(seed), EarlyStopping(val_loss, patience,
+        restore_best_weights=True).
+
+        Early stopping is `val_loss < best` with a wait counter against patience.
+        The best epoch's weights are kept on the host and installed at the end
+        whether or not training stopped early (Keras restores them only on an
+        early stop; the last epoch's weights are installed only if no epoch's
+        val_loss was ever finite).
+
+        Returns {'loss': [...], 'val_loss': [...], 'best_epoch', 'stopped_epoch'}
+        (kinematics/train.py early_stopping_loop).  Afterwards predict() and
+        save_model() work as for a loaded model."""
+        from . import train as T
+        x = np.asarray(samples, dtype=np.float64)
+        y = np.asarray(features, dtype=np.float64)
+        if x.ndim != 2 or y.ndim != 2 or x.shape[0] != y.shape[0]:
+            raise ValueError(f"samples {x.shape} / features {y.shape}: expected two 2D arrays "
+                             "with the same number of rows")
+        tr, te = T.split_indices(x.shape[0], test_size, split_seed)
+        xs, ys = T.fit_scaler(x[tr]), T.fit_scaler(y[tr])
+        x_tr = xs.transform(x[tr]).astype(np.float32)
+        y_tr = ys.transform(y[tr]).astype(np.float32)
+        x_te = xs.transform(x[te]).astype(np.float32)
+        y_te = ys.transform(y[te]).astype(np.float32)
+        dims, acts = [x.shape[1]], []
+        for count, units, act in T.parse_hidden(hidden):
+            dims += [units] * count
+            acts += [act] * count
+        dims.append(y.shape[1])
+        acts.append("linear")
+        model = glorot_model(tuple(dims), seed=seed)
+        model.activations = acts
+        perm = T.epoch_permutations(seed)
+        ctx = _native.context()
+        ctx.train_begin(model.weights, model.biases, acts,
+                        max_batch=max(int(batch_size), min(4096, len(te))), lr=learning_rate)
+        try:
+            ctx.train_data(x_tr, y_tr, x_te, y_te)
+            hist, best = T.early_stopping_loop(
+                epochs, patience, lambda e: ctx.train_epoch(perm(len(tr)), int(batch_size)),
+                lambda: ctx.train_get("weights"), verbose)
+            if best is None and hist["loss"]:
+                best = ctx.train_get("weights")
+        finally:
+            ctx.train_end()
+        if best is not None:
+            model.weights, model.biases = list(best[0]), list(best[1])
+        model.name = "sequential"
+        self.set_model(model, xs, ys)
+        return hist
 
     def set_model(self, model: DenseModel, x_scaler: ScalerParams, y_scaler: ScalerParams):
         """Install an in-memory model (e.g. glorot_model()) and its scalers."""
