@@ -173,6 +173,36 @@ int ik_ann_load(ik_ctx *ctx, int n_layers, const int32_t *dims, const int32_t *a
 int ik_ann_solve(ik_ctx *ctx, const double *pts, int64_t n, float *ang, double *fk_err,
                  int flags, ik_stats *stats);
 
+/* ---- Refine ------------------------------------------------------------------
+ * Damped-least-squares polish of seed angles towards pts, float64, for the
+ * context's robot (any DH table of 4 revolute joints).  Per row, with theta the
+ * seed wrapped to [-pi, pi] (theta - 2 pi rint(theta / 2 pi)):
+ *   e = p - FK(theta), err = |e|; stop when !(err > tol) or after max_iter steps;
+ *   delta = J^T (J J^T + damping^2 I)^-1 e with the analytic 3 x 4 Jacobian (LDL^T);
+ *   delta is scaled so that max |delta_i| <= 0.5 rad; theta = wrap(theta + delta).
+ * pts n x 3, seed n x 4, ang n x 4 (float64); iters (nullable) n int32: steps
+ * taken; fk_err (nullable) n float64: the error the stop test saw (<= tol for a
+ * converged row, NaN for a NaN goal or seed, which takes no step).  stats:
+ * max_iters / sum_iters over the rows, n_capped = rows with !(err <= tol),
+ * max_fk_err / sum_fk_err over the finite errors, first_oob as for the other
+ * solves (the rows are still solved); first_err stays -1.  A goal out of reach, or
+ * on the line of a fully stretched seed, ends at max_iter with finite angles.
+ * IK_E_BADARG: n < 0, a NULL pts / seed / ang with n > 0, max_iter < 0, tol NaN,
+ * damping not finite or <= 0, IK_F_ASYNC without IK_F_DEVICE, a device ang not
+ * 16-byte aligned. */
+int ik_refine(ik_ctx *ctx, const double *pts, const double *seed, int64_t n, double tol,
+              int32_t max_iter, double damping, double *ang, int32_t *iters /*nullable*/,
+              double *fk_err /*nullable*/, int flags, ik_stats *stats);
+
+/* ik_ann_solve, then ik_refine seeded with the network's float32 angles, in one
+ * call on the context's stream: the seeds stay in device scratch.  seed_fk_err
+ * (nullable): the network's own |FK - p| (what ik_ann_solve's fk_err would hold).
+ * iters / fk_err nullable.  stats describe the refined result.  IK_E_NOMODEL
+ * before ik_ann_load. */
+int ik_ann_solve_refined(ik_ctx *ctx, const double *pts, int64_t n, double tol, int32_t max_iter,
+                         double damping, double *ang, int32_t *iters, double *fk_err,
+                         double *seed_fk_err, int flags, ik_stats *stats);
+
 /* Arithmetic of the hidden-layer GEMMs.  IK_ANN_FP32 (default): fp32 MFMA
  * (v_mfma_f32_32x32x2_f32), a fp32 dot product like the reference's TF/Keras
  * CPU float32 forward.  IK_ANN_BF16X6: every fp32 operand split into three bf16

@@ -33,6 +33,7 @@ ACTS = {"linear": 0, "tanh": 1, "relu": 2, "sigmoid": 3}
 EXPORTED_SYMBOLS = ("ik_ctx_create", "ik_ctx_destroy", "ik_ctx_set_stream", "ik_ctx_get_stream",
                     "ik_last_error", "ik_version", "ik_set_robot", "ik_check_limits", "ik_fk", "ik_fk_chain",
                     "ik_fabrik_solve", "ik_fabrik_solve_fk", "ik_fabrik_calc", "ik_fabrik_reset_order", "ik_ann_load", "ik_ann_solve",
+                    "ik_refine", "ik_ann_solve_refined",
                     "ik_stats_fetch", "ik_ctx_set_timing", "ik_kernel_times",
                     "ik_ctx_set_debug", "ik_debug_read", "ik_ann_set_mode", "ik_ann_get_mode",
                     "ik_ann_effective_mode",
@@ -132,6 +133,10 @@ def load_library(path: str = LIB_PATH):
         L.ik_ann_load.argtypes = [vp, ctypes.c_int, ip, ip, ctypes.POINTER(ctypes.c_void_p),
                                   ctypes.POINTER(ctypes.c_void_p), dp, dp, dp, dp]
         L.ik_ann_solve.argtypes = [vp, dp, i64, dp, dp, ctypes.c_int, st]
+        L.ik_refine.argtypes = [vp, dp, dp, i64, ctypes.c_double, i32, ctypes.c_double, dp, ip, dp,
+                                ctypes.c_int, st]
+        L.ik_ann_solve_refined.argtypes = [vp, dp, i64, ctypes.c_double, i32, ctypes.c_double, dp,
+                                           ip, dp, dp, ctypes.c_int, st]
         L.ik_stats_fetch.argtypes = [vp, st]
         L.ik_ctx_sync.argtypes = [vp]
         L.ik_comm_set_timeout.argtypes = [vp, ctypes.c_double]
@@ -486,6 +491,73 @@ class Context:
                 self._dev(fk_err, "float64", (n,), "fk_err"))
         self._on_torch_stream(lambda: self._check(self.lib.ik_ann_solve(
             self.handle, args[0], n, args[1], args[2], flags, ctypes.byref(s))))
+        return s
+
+    # -- refine (include/ikhip.h "Refine") -------------------------------------
+    def refine(self, pts, seed, tol=1e-6, max_iter=20, damping=1e-3, check_limits=True,
+               want_iters=True, want_fk_err=True):
+        """Damped-least-squares polish of seed (n x 4) towards pts (n x 3), host arrays:
+        returns (angles n x 4 f64, iters or None, fk_err or None, stats)."""
+        s = IkStats()
+        p = _host(pts, np.float64, 3)
+        sd = _host(seed, np.float64, 4)
+        n = p.shape[0]
+        if sd.shape[0] != n:
+            raise ValueError(f"seed: {sd.shape[0]} rows for {n} points")
+        ang = np.empty((n, 4), np.float64)
+        it = np.empty(n, np.int32) if want_iters else None
+        err = np.empty(n, np.float64) if want_fk_err else None
+        flags = 0 if check_limits else IK_F_NO_LIMITS
+        self._check(self.lib.ik_refine(self.handle, _ptr(p), _ptr(sd), n, float(tol),
+                                       int(max_iter), float(damping), _ptr(ang), _ptr(it),
+                                       _ptr(err), flags, ctypes.byref(s)))
+        return ang, it, err, s
+
+    def refine_device(self, pts, seed, ang, iters=None, fk_err=None, tol=1e-6, max_iter=20,
+                      damping=1e-3, flags: int = IK_F_DEVICE):
+        s = IkStats()
+        n = int(pts.shape[0])
+        args = (self._dev(pts, "float64", (n, 3), "pts"),
+                self._dev(seed, "float64", (n, 4), "seed"),
+                self._dev(ang, "float64", (n, 4), "ang"),
+                self._dev(iters, "int32", (n,), "iters"),
+                self._dev(fk_err, "float64", (n,), "fk_err"))
+        self._on_torch_stream(lambda: self._check(self.lib.ik_refine(
+            self.handle, args[0], args[1], n, float(tol), int(max_iter), float(damping), args[2],
+            args[3], args[4], flags, ctypes.byref(s))))
+        return s
+
+    def ann_solve_refined(self, pts, tol=1e-6, max_iter=20, damping=1e-3, check_limits=True,
+                          want_seed_fk_err=False):
+        """ANN solve + refine in one call (ik_ann_solve_refined): returns (angles
+        n x 4 f64, iters, fk_err, seed_fk_err or None, stats)."""
+        s = IkStats()
+        p = _host(pts, np.float64, 3)
+        n = p.shape[0]
+        ang = np.empty((n, 4), np.float64)
+        it = np.empty(n, np.int32)
+        err = np.empty(n, np.float64)
+        serr = np.empty(n, np.float64) if want_seed_fk_err else None
+        flags = 0 if check_limits else IK_F_NO_LIMITS
+        self._check(self.lib.ik_ann_solve_refined(self.handle, _ptr(p), n, float(tol),
+                                                  int(max_iter), float(damping), _ptr(ang),
+                                                  _ptr(it), _ptr(err), _ptr(serr), flags,
+                                                  ctypes.byref(s)))
+        return ang, it, err, serr, s
+
+    def ann_solve_refined_device(self, pts, ang, iters=None, fk_err=None, seed_fk_err=None,
+                                 tol=1e-6, max_iter=20, damping=1e-3,
+                                 flags: int = IK_F_DEVICE):
+        s = IkStats()
+        n = int(pts.shape[0])
+        args = (self._dev(pts, "float64", (n, 3), "pts"),
+                self._dev(ang, "float64", (n, 4), "ang"),
+                self._dev(iters, "int32", (n,), "iters"),
+                self._dev(fk_err, "float64", (n,), "fk_err"),
+                self._dev(seed_fk_err, "float64", (n,), "seed_fk_err"))
+        self._on_torch_stream(lambda: self._check(self.lib.ik_ann_solve_refined(
+            self.handle, args[0], n, float(tol), int(max_iter), float(damping), args[1], args[2],
+            args[3], args[4], flags, ctypes.byref(s))))
         return s
 
     # -- training (include/ikhip.h "ANN training") ---------------------------

@@ -12,7 +12,10 @@ ValueError are printed and the command still exits 0 (cli.py:250-252, 300),
 a ZeroDivisionError propagates.  Plotting (plot/plot.py) is out of scope:
 --verbose prints the angles and the FK round-trip error instead of plotting.
 Extra flags: --tol / --max-iter (FABRIK, defaults 1e-3 / 100 as the
-reference's constructor) and --device.
+reference's constructor), --device, and for --method ann --refine-tol FLOAT
+[--refine-iter INT, default 20]: the network's angles are polished on the GPU by
+the damped-least-squares refine (kinematics/refine.py) and written as float64;
+--verbose then reports the network's and the polished FK error.
 `--generate-data --shape {circle,cube,cube_random,random,spring,random_dist}` runs
 the reference's generators (robot/position_generator.py, cli.py:80-229) with the
 same arguments: --to-file writes the x,y,z CSV, --verbose prints the shape's
@@ -61,6 +64,9 @@ def _parser():
     p.add_argument("--tol", type=float, default=0.001, help="FABRIK error margin")
     p.add_argument("--max-iter", type=int, default=100, help="FABRIK iteration cap")
     p.add_argument("--device", type=int, default=None, help="GPU index")
+    p.add_argument("--refine-tol", type=float, default=None,
+                   help="ANN: polish the angles until |FK(theta) - p| <= this")
+    p.add_argument("--refine-iter", type=int, default=20, help="ANN: refine step cap")
     # data generators
     p.add_argument("--samples", type=int)
     p.add_argument("--dim", type=str)
@@ -108,11 +114,16 @@ def _ikine(args, parser):
         parser.error("the following arguments are required: --points")
     if args.method == "ann" and args.model is None:
         parser.error("the following arguments are required: --model")
+    if args.refine_tol is not None and args.method != "ann":
+        parser.error("--refine-tol is only valid with --method ann")
     from .kinematics.inverse import AnnInverseKinematics, FabrikInverseKinematics
     points = _read_points(args.points)
     dh = [list(r) for r in Robot.dh_matrix]
     if args.method == "ann":
-        ik = AnnInverseKinematics(dh, Robot.links_lengths, Robot.effector_workspace_limits)
+        refine = (None if args.refine_tol is None
+                  else {"tol": args.refine_tol, "max_iter": args.refine_iter})
+        ik = AnnInverseKinematics(dh, Robot.links_lengths, Robot.effector_workspace_limits,
+                                  refine=refine)
         ik.load_model(args.model)
     else:
         ik = FabrikInverseKinematics(dh, Robot.links_lengths, Robot.effector_workspace_limits,
@@ -124,6 +135,12 @@ def _ikine(args, parser):
         return 0
     if args.verbose:
         _verbose(points, joint_angles)
+        if args.refine_tol is not None:
+            seed, it = ik.last_seed_fk_err, ik.last_iterations
+            print(f"ANN seed: max |FK(theta) - p| = {seed.max():.6g}, mean = {seed.mean():.6g}; "
+                  f"refined to tol {args.refine_tol:g} in max {int(it.max())} steps "
+                  f"(mean {it.mean():.3g}), {ik.last_stats.n_capped} of {len(it)} points not "
+                  "converged")
     if args.to_file is not None:
         _save_angles(joint_angles, args.to_file)
     return 0

@@ -975,6 +975,120 @@ int ik_ann_solve(ik_ctx *c, const double *pts, int64_t n, float *ang, double *fk
   return finish(c, flags, stats);
 }
 
+// ---- refine (ik_refine.hip) ----------------------------------------------------
+static int refine_args(const char *who, ik_ctx *c, int64_t n, bool arrays, double tol,
+                       int32_t max_iter, double damping, const double *ang, int flags) {
+  const std::string w(who);
+  if (!c || n < 0 || (n > 0 && !arrays) || max_iter < 0) return fail(IK_E_BADARG, w + ": bad args");
+  if (std::isnan(tol)) return fail(IK_E_BADARG, w + ": tol is NaN");
+  if (!std::isfinite(damping) || !(damping > 0.0))
+    return fail(IK_E_BADARG, w + ": damping must be finite and > 0");
+  if ((flags & IK_F_ASYNC) && !(flags & IK_F_DEVICE))
+    return fail(IK_E_BADARG, "IK_F_ASYNC requires IK_F_DEVICE");
+  if ((flags & IK_F_DEVICE) && (reinterpret_cast<uintptr_t>(ang) & 15))
+    return fail(IK_E_BADARG, w + ": device ang must be 16-byte aligned");
+  return IK_OK;
+}
+
+int ik_refine(ik_ctx *c, const double *pts, const double *seed, int64_t n, double tol,
+              int32_t max_iter, double damping, double *ang, int32_t *iters, double *fk_err,
+              int flags, ik_stats *stats) {
+  int rc = refine_args("ik_refine", c, n, pts && seed && ang, tol, max_iter, damping, ang, flags);
+  if (rc) return rc;
+  if ((rc = set_dev(c))) return rc;
+  KtScope kts(c);
+  const bool dev = flags & IK_F_DEVICE;
+  const double *dp = pts, *ds = seed;
+  double *da = ang, *dfe = fk_err;
+  int32_t *di = iters;
+  if (!dev) {
+    const size_t b_in = Stage::up((size_t)n * 24), b_sd = Stage::up((size_t)n * 32),
+                 b_ang = Stage::up((size_t)n * 32), b_it = iters ? Stage::up((size_t)n * 4) : 0,
+                 b_fe = fk_err ? Stage::up((size_t)n * 8) : 0;
+    if ((rc = ensure_scratch(c, b_in + b_sd + b_ang + b_it + b_fe))) return rc;
+    char *q = static_cast<char *>(c->scratch);
+    IK_HIP(hipMemcpyAsync(q, pts, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
+    dp = reinterpret_cast<double *>(q);
+    q += b_in;
+    IK_HIP(hipMemcpyAsync(q, seed, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+    ds = reinterpret_cast<double *>(q);
+    q += b_sd;
+    da = reinterpret_cast<double *>(q);
+    q += b_ang;
+    di = iters ? reinterpret_cast<int32_t *>(q) : nullptr;
+    q += b_it;
+    dfe = fk_err ? reinterpret_cast<double *>(q) : nullptr;
+  }
+  launch_reset_stats(c->d_stats, c->stream);
+  launch_refine(c->rconst, dp, ds, n, tol, max_iter, damping, da, di, dfe,
+                !(flags & IK_F_NO_LIMITS), c->d_stats, c->stream);
+  IK_HIP(hipGetLastError());
+  if (!dev && n > 0) {
+    IK_HIP(hipMemcpyAsync(ang, da, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+    if (iters)
+      IK_HIP(hipMemcpyAsync(iters, di, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (fk_err)
+      IK_HIP(hipMemcpyAsync(fk_err, dfe, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  return finish(c, flags, stats);
+}
+
+int ik_ann_solve_refined(ik_ctx *c, const double *pts, int64_t n, double tol, int32_t max_iter,
+                         double damping, double *ang, int32_t *iters, double *fk_err,
+                         double *seed_fk_err, int flags, ik_stats *stats) {
+  int rc = refine_args("ik_ann_solve_refined", c, n, pts && ang, tol, max_iter, damping, ang,
+                       flags);
+  if (rc) return rc;
+  if (!c->ann_loaded)
+    return fail(IK_E_NOMODEL, "ik_ann_solve_refined: no model loaded (ik_ann_load)");
+  if ((rc = set_dev(c))) return rc;
+  KtScope kts(c);
+  const bool dev = flags & IK_F_DEVICE;
+  const bool limits = !(flags & IK_F_NO_LIMITS);
+  // the network's float32 angles never leave the device: they are the refine's seeds
+  const size_t b_seed = Stage::up((size_t)n * 16);
+  const size_t b_in = dev ? 0 : Stage::up((size_t)n * 24);
+  const size_t b_ang = dev ? 0 : Stage::up((size_t)n * 32);
+  const size_t b_it = (dev || !iters) ? 0 : Stage::up((size_t)n * 4);
+  const size_t b_fe = (dev || !fk_err) ? 0 : Stage::up((size_t)n * 8);
+  const size_t b_se = (dev || !seed_fk_err) ? 0 : Stage::up((size_t)n * 8);
+  if ((rc = ensure_scratch(c, b_seed + b_in + b_ang + b_it + b_fe + b_se))) return rc;
+  char *q = static_cast<char *>(c->scratch);
+  float *dseed = reinterpret_cast<float *>(q);
+  q += b_seed;
+  const double *dp = pts;
+  double *da = ang, *dfe = fk_err, *dse = seed_fk_err;
+  int32_t *di = iters;
+  if (!dev) {
+    IK_HIP(hipMemcpyAsync(q, pts, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
+    dp = reinterpret_cast<double *>(q);
+    q += b_in;
+    da = reinterpret_cast<double *>(q);
+    q += b_ang;
+    di = iters ? reinterpret_cast<int32_t *>(q) : nullptr;
+    q += b_it;
+    dfe = fk_err ? reinterpret_cast<double *>(q) : nullptr;
+    q += b_fe;
+    dse = seed_fk_err ? reinterpret_cast<double *>(q) : nullptr;
+  }
+  if ((rc = ann_launch(c, dp, n, dseed, dse, limits))) return rc;
+  // the call's stats are the refined result's
+  launch_reset_stats(c->d_stats, c->stream);
+  launch_refine_f32(c->rconst, dp, dseed, n, tol, max_iter, damping, da, di, dfe, limits,
+                    c->d_stats, c->stream);
+  IK_HIP(hipGetLastError());
+  if (!dev && n > 0) {
+    IK_HIP(hipMemcpyAsync(ang, da, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+    if (iters)
+      IK_HIP(hipMemcpyAsync(iters, di, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (fk_err)
+      IK_HIP(hipMemcpyAsync(fk_err, dfe, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (seed_fk_err)
+      IK_HIP(hipMemcpyAsync(seed_fk_err, dse, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  return finish(c, flags, stats);
+}
+
 }  // extern "C"
 
 // ---- training (ik_train.hip) -------------------------------------------------

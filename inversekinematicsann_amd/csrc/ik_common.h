@@ -562,6 +562,15 @@ bool robot_const_current(const RobotDev &r);
 void launch_fabrik_calc(int nj, const double *dists, const double *init, bool init_shared,
                         const double *goals, int64_t n, double tol, int max_iter,
                         double *joints, int32_t *iters, DevStats *S, hipStream_t st);
+// Damped-least-squares refine (ik_refine.hip) of seed angles (n x 4, float64 or
+// the ANN's float32) towards pts; rc: the robot's constants (device).  iters /
+// fk_err nullable; iteration and FK-error stats into S.
+void launch_refine(const RobotConstDev *rc, const double *pts, const double *seed, int64_t n,
+                   double tol, int max_iter, double damping, double *ang, int32_t *iters,
+                   double *fk_err, bool check_limits, DevStats *S, hipStream_t st);
+void launch_refine_f32(const RobotConstDev *rc, const double *pts, const float *seed, int64_t n,
+                       double tol, int max_iter, double damping, double *ang, int32_t *iters,
+                       double *fk_err, bool check_limits, DevStats *S, hipStream_t st);
 
 constexpr int kAnnMaxLayers = 24;
 constexpr int kAnnMaxWidth = 1024;  // > 512: the wide build (ik_ann_w.hip), fp32 only

@@ -1,0 +1,244 @@
+// ik_refine.hip -- damped-least-squares polish of seed angles (ik_refine,
+// ik_ann_solve_refined; DESIGN.md section 3 "Refine").
+//
+// One goal per lane, fp64 VALU, everything in registers.  Per step: the FK chain
+// of fk_error_cs (ik_common.h) applied right to left to a vector, with the four
+// Jacobian columns riding along -- d Rz(t_i) v / dt_i = (-y', x', 0) of the rotated
+// (x', y'), then only the rotations to its left -- A = J J^T + lambda^2 I (3 x 3,
+// six entries), LDL^T without pivoting, delta = J^T A^-1 e, the 0.5 rad clamp and
+// the wrap to [-pi, pi].  kinematics/refine.py restates it operation for operation;
+// the only difference is sincos_fk against libm's sin / cos (<= 1.2e-16).
+//
+// The wave iterates until no lane is active; a finished lane keeps its angles (the
+// update is a select) and recomputes the same error.  HBM per row: 24 B goal +
+// 32 / 16 B seed in, 32 B angles (+ 4 B count + 8 B error) out.
+#include "ik_common.h"
+
+namespace ikhip {
+
+constexpr double kTwoPi = 2 * kPi;
+constexpr double kRefineClamp = 0.5;  // largest |delta_i| of one step, radians
+
+// theta - 2 pi rint(theta / 2 pi): in [-pi, pi] (exact for |theta| <= 8 pi)
+__device__ __forceinline__ double wrap_pi(double t) {
+  return t - kTwoPi * __builtin_rint(t / kTwoPi);
+}
+
+template <typename SeedT>
+__global__ __launch_bounds__(256) void refine_kernel(const RobotConstDev *rc, const double *pts,
+                                                     const SeedT *seed, int64_t n, double tol,
+                                                     int max_iter, double lam2, double *ang,
+                                                     int32_t *iters, double *fk_err,
+                                                     int check_limits, DevStats *S) {
+  const RcConst k = (RcConst)rc;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = i < n;
+  double px = 0.0, py = 0.0, pz = 0.0, t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
+  if (valid) {
+    px = pts[3 * i];
+    py = pts[3 * i + 1];
+    pz = pts[3 * i + 2];
+    t0 = wrap_pi((double)seed[4 * i]);
+    t1 = wrap_pi((double)seed[4 * i + 1]);
+    t2 = wrap_pi((double)seed[4 * i + 2]);
+    t3 = wrap_pi((double)seed[4 * i + 3]);
+    if (check_limits) {
+      const double lim[6] = {k->lim[0], k->lim[1], k->lim[2], k->lim[3], k->lim[4], k->lim[5]};
+      if (outside(lim, px, py, pz)) atomicMin(&S->first_oob, (unsigned long long)i);
+    }
+  }
+  // B_i = Tz(d_i) Tx(a_i) Rx(alpha_i): jc[i] = {a_i, d_i, cos alpha_i, sin alpha_i}
+  const double a1 = k->jc[0], d1 = k->jc[1], ca1 = k->jc[2], sa1 = k->jc[3];
+  const double a2 = k->jc[4], d2 = k->jc[5], ca2 = k->jc[6], sa2 = k->jc[7];
+  const double a3 = k->jc[8], d3_ = k->jc[9], ca3 = k->jc[10], sa3 = k->jc[11];
+  const double a4 = k->jc[12], d4 = k->jc[13];
+  const bool alpha_ok = !k->alpha_bad;  // some |alpha_i| > 2 pi: FK raises, the error is NaN
+
+  bool active = valid;
+  int it = 0;
+  double err = 0.0;
+  for (;;) {
+    double s0, c0, s1, c1, s2, c2, s3, c3;
+    sincos_fk(t0, &s0, &c0);
+    sincos_fk(t1, &s1, &c1);
+    sincos_fk(t2, &s2, &c2);
+    sincos_fk(t3, &s3, &c3);
+    // ---- joint 4: v = B4 e4 = (a4, 0, d4); Rz(t4)
+    double x = a4, y = 0.0, z = d4;
+    double xr = c3 * x - s3 * y, yr = s3 * x + c3 * y;
+    double j3x = -yr, j3y = xr, j3z = 0.0;  // column 4
+    x = xr;
+    y = yr;
+    // B3, then its rotation on the open column
+    double yb = ca3 * y - sa3 * z, zb = sa3 * y + ca3 * z + d3_;
+    x = x + a3;
+    y = yb;
+    z = zb;
+    double wy = ca3 * j3y - sa3 * j3z, wz = sa3 * j3y + ca3 * j3z;
+    j3y = wy;
+    j3z = wz;
+    // ---- joint 3: Rz(t3)
+    xr = c2 * x - s2 * y;
+    yr = s2 * x + c2 * y;
+    double j2x = -yr, j2y = xr, j2z = 0.0;  // column 3
+    x = xr;
+    y = yr;
+    double wx = c2 * j3x - s2 * j3y;
+    wy = s2 * j3x + c2 * j3y;
+    j3x = wx;
+    j3y = wy;
+    // B2
+    yb = ca2 * y - sa2 * z;
+    zb = sa2 * y + ca2 * z + d2;
+    x = x + a2;
+    y = yb;
+    z = zb;
+    wy = ca2 * j3y - sa2 * j3z;
+    wz = sa2 * j3y + ca2 * j3z;
+    j3y = wy;
+    j3z = wz;
+    wy = ca2 * j2y - sa2 * j2z;
+    wz = sa2 * j2y + ca2 * j2z;
+    j2y = wy;
+    j2z = wz;
+    // ---- joint 2: Rz(t2)
+    xr = c1 * x - s1 * y;
+    yr = s1 * x + c1 * y;
+    double j1x = -yr, j1y = xr, j1z = 0.0;  // column 2
+    x = xr;
+    y = yr;
+    wx = c1 * j3x - s1 * j3y;
+    wy = s1 * j3x + c1 * j3y;
+    j3x = wx;
+    j3y = wy;
+    wx = c1 * j2x - s1 * j2y;
+    wy = s1 * j2x + c1 * j2y;
+    j2x = wx;
+    j2y = wy;
+    // B1
+    yb = ca1 * y - sa1 * z;
+    zb = sa1 * y + ca1 * z + d1;
+    x = x + a1;
+    y = yb;
+    z = zb;
+    wy = ca1 * j3y - sa1 * j3z;
+    wz = sa1 * j3y + ca1 * j3z;
+    j3y = wy;
+    j3z = wz;
+    wy = ca1 * j2y - sa1 * j2z;
+    wz = sa1 * j2y + ca1 * j2z;
+    j2y = wy;
+    j2z = wz;
+    wy = ca1 * j1y - sa1 * j1z;
+    wz = sa1 * j1y + ca1 * j1z;
+    j1y = wy;
+    j1z = wz;
+    // ---- joint 1: Rz(t1)
+    xr = c0 * x - s0 * y;
+    yr = s0 * x + c0 * y;
+    const double j0x = -yr, j0y = xr;  // column 1 (its z is 0)
+    x = xr;
+    y = yr;
+    wx = c0 * j3x - s0 * j3y;
+    wy = s0 * j3x + c0 * j3y;
+    j3x = wx;
+    j3y = wy;
+    wx = c0 * j2x - s0 * j2y;
+    wy = s0 * j2x + c0 * j2y;
+    j2x = wx;
+    j2y = wy;
+    wx = c0 * j1x - s0 * j1y;
+    wy = s0 * j1x + c0 * j1y;
+    j1x = wx;
+    j1y = wy;
+
+    const double ex = px - x, ey = py - y, ez = pz - z;
+    const double en = sqrt(ex * ex + ey * ey + ez * ez);
+    if (active) {
+      err = alpha_ok ? en : __builtin_nan("");
+      if (!(err > tol) || it == max_iter) active = false;
+    }
+    if (!__any(active)) break;
+
+    // A = J J^T + lambda^2 I (rows x, y, z; column 1 has no z part)
+    const double A00 = j0x * j0x + j1x * j1x + j2x * j2x + j3x * j3x + lam2;
+    const double A10 = j0y * j0x + j1y * j1x + j2y * j2x + j3y * j3x;
+    const double A11 = j0y * j0y + j1y * j1y + j2y * j2y + j3y * j3y + lam2;
+    const double A20 = j1z * j1x + j2z * j2x + j3z * j3x;
+    const double A21 = j1z * j1y + j2z * j2y + j3z * j3y;
+    const double A22 = j1z * j1z + j2z * j2z + j3z * j3z + lam2;
+    // LDL^T, no pivoting (A is SPD)
+    const double l10 = A10 / A00, l20 = A20 / A00;
+    const double D1 = A11 - l10 * A10;
+    const double u21 = A21 - l20 * A10;
+    const double l21 = u21 / D1;
+    const double D2 = A22 - l20 * A20 - l21 * u21;
+    const double y1 = ey - l10 * ex;
+    const double y2 = ez - l20 * ex - l21 * y1;
+    const double q2 = y2 / D2;
+    const double q1 = y1 / D1 - l21 * q2;
+    const double q0 = ex / A00 - l10 * q1 - l20 * q2;
+    // delta = J^T q
+    double e0 = j0x * q0 + j0y * q1;
+    double e1 = j1x * q0 + j1y * q1 + j1z * q2;
+    double e2 = j2x * q0 + j2y * q1 + j2z * q2;
+    double e3 = j3x * q0 + j3y * q1 + j3z * q2;
+    const double m = fmax(fmax(fabs(e0), fabs(e1)), fmax(fabs(e2), fabs(e3)));
+    if (m > kRefineClamp) {
+      const double sc = kRefineClamp / m;
+      e0 = e0 * sc;
+      e1 = e1 * sc;
+      e2 = e2 * sc;
+      e3 = e3 * sc;
+    }
+    if (active) {
+      t0 = wrap_pi(t0 + e0);
+      t1 = wrap_pi(t1 + e1);
+      t2 = wrap_pi(t2 + e2);
+      t3 = wrap_pi(t3 + e3);
+      ++it;
+    }
+  }
+
+  if (valid) {
+    double2 *o = reinterpret_cast<double2 *>(ang + 4 * i);
+    o[0] = make_double2(t0, t1);
+    o[1] = make_double2(t2, t3);
+    if (iters) iters[i] = it;
+    if (fk_err) fk_err[i] = err;
+  }
+  // n_capped: rows that did not converge (a NaN error included)
+  block_iter_stats_acc(S, valid ? (unsigned long long)it : 0ull,
+                       (valid && !(err <= tol)) ? 1ull : 0ull, valid ? it : 0);
+  const double fe = (valid && err <= 1.7976931348623157e308) ? err : 0.0;  // finite (not NaN)
+  wave_fk_stats(S, fe, fe);
+}
+
+template <typename SeedT>
+static void launch_refine_t(const RobotConstDev *rc, const double *pts, const SeedT *seed,
+                            int64_t n, double tol, int max_iter, double damping, double *ang,
+                            int32_t *iters, double *fk_err, bool check_limits, DevStats *S,
+                            hipStream_t st) {
+  if (n <= 0) return;
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  kt_begin("refine_kernel", st);
+  IK_LAUNCH(refine_kernel<SeedT>, dim3(grid), dim3(256), 0, st, rc, pts, seed, n, tol, max_iter,
+            damping * damping, ang, iters, fk_err, check_limits ? 1 : 0, S);
+  kt_end(st);
+}
+
+void launch_refine(const RobotConstDev *rc, const double *pts, const double *seed, int64_t n,
+                   double tol, int max_iter, double damping, double *ang, int32_t *iters,
+                   double *fk_err, bool check_limits, DevStats *S, hipStream_t st) {
+  launch_refine_t(rc, pts, seed, n, tol, max_iter, damping, ang, iters, fk_err, check_limits, S,
+                  st);
+}
+
+void launch_refine_f32(const RobotConstDev *rc, const double *pts, const float *seed, int64_t n,
+                       double tol, int max_iter, double damping, double *ang, int32_t *iters,
+                       double *fk_err, bool check_limits, DevStats *S, hipStream_t st) {
+  launch_refine_t(rc, pts, seed, n, tol, max_iter, damping, ang, iters, fk_err, check_limits, S,
+                  st);
+}
+
+}  // namespace ikhip

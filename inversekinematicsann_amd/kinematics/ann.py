@@ -227,6 +227,17 @@ class ANN:
         ang, err, st = self._ctx().ann_solve(pts, check_limits=False, want_fk_err=True)
         return ang, err, st
 
+    def predict_refined(self, position, tol=1e-6, max_iter=20, damping=1e-3, check_limits=False,
+                        want_seed_fk_err=False):
+        """predict + the damped-least-squares refine of the network's angles in one
+        library call (ik_ann_solve_refined): (angles n x 4 float64, iters, fk_err,
+        stats); with want_seed_fk_err the network's own |FK - p| is appended."""
+        pts = as_features(position)
+        ang, it, err, serr, st = self._ctx().ann_solve_refined(
+            pts, tol=tol, max_iter=max_iter, damping=damping, check_limits=check_limits,
+            want_seed_fk_err=want_seed_fk_err)
+        return (ang, it, err, st, serr) if want_seed_fk_err else (ang, it, err, st)
+
     def load_model(self, model_h5):
         """Load model from file (ann.py:78-85)."""
         if model_h5.endswith(".npz"):

@@ -133,21 +133,43 @@ class FabrikInverseKinematics(InverseKinematics):
 class AnnInverseKinematics(InverseKinematics):
     """Reaching inverse kinematics using the ANN method (inverse.py:142-155)."""
 
-    def __init__(self, dh_matrix, joints_distances, workspace_limits):
+    def __init__(self, dh_matrix, joints_distances, workspace_limits, refine=None):
+        """refine: None (the reference's behaviour: the network's float32 angles),
+        True, or a dict with any of tol / max_iter / damping: ikine then returns the
+        angles polished by the library's damped-least-squares refine (float64;
+        defaults 1e-6 / 20 / 1e-3, kinematics/refine.py) and sets last_iterations,
+        last_fk_err and last_seed_fk_err."""
         super().__init__(dh_matrix, joints_distances, workspace_limits)
         self.ann = ANN(workspace_limits, dh_matrix)
+        if refine is None or refine is False:
+            self.refine = None
+        else:
+            opts = {} if refine is True else dict(refine)
+            unknown = set(opts) - {"tol", "max_iter", "damping"}
+            if unknown:
+                raise ValueError(f"refine: unknown options {sorted(unknown)}")
+            self.refine = opts
+        self.last_iterations = None
+        self.last_fk_err = None
+        self.last_seed_fk_err = None
 
     def load_model(self, model_name):
         """Load a model (.h5 + _scaler_{x,y}.bin, or .npz) onto the GPU."""
         self.ann.load_model(model_name)
 
     def ikine(self, dest_points):
-        """Predicted joint angles (float32 values as Python floats)."""
+        """Predicted joint angles (float32 values as Python floats); with refine,
+        the polished float64 angles."""
         pts = as_ann_points(dest_points)
         if pts.shape[0] == 0:
             return []
         self._ctx()
-        ang, st = self.ann.predict_checked(pts)
+        if self.refine is not None:
+            ang, it, err, st, serr = self.ann.predict_refined(
+                pts, check_limits=True, want_seed_fk_err=True, **self.refine)
+            self.last_iterations, self.last_fk_err, self.last_seed_fk_err = it, err, serr
+        else:
+            ang, st = self.ann.predict_checked(pts)
         self.last_stats = st
         if st.first_oob >= 0:
             self._raise_out_of_reach(dest_points, st.first_oob)
