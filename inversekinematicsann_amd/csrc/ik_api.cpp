@@ -144,8 +144,45 @@ int ensure_scratch(ik_ctx *c, size_t bytes) {
   return IK_OK;
 }
 
+int Stage::add(Kind kind, const void *user, size_t bytes) {
+  if (n_ >= kMax) {  // refused by reserve()
+    n_ = kMax + 1;
+    return 0;
+  }
+  const bool staged = kind == kWork || kind == kTable || (!dev_ && (kind == kIn || user));
+  r_[n_] = {kind, const_cast<void *>(user), bytes, staged ? cv_.add(bytes) : 0, staged, nullptr};
+  return n_++;
+}
+
+int Stage::reserve() {
+  if (n_ > kMax) return fail(IK_E_BADARG, "Stage: more than kMax regions");
+  const int rc = ensure_scratch(c_, cv_.total);
+  if (rc) return rc;
+  for (Region *r = r_; r != r_ + n_; ++r) {
+    r->dev = r->staged ? static_cast<char *>(c_->scratch) + r->off : r->user;
+    if (r->staged && (r->kind == kTable || r->kind == kIn) && r->bytes)
+      IK_HIP(hipMemcpyAsync(r->dev, r->user, r->bytes, hipMemcpyHostToDevice, c_->stream));
+  }
+  return IK_OK;
+}
+
+int Stage::flush() {
+  for (const Region *r = r_; r != r_ + n_; ++r)
+    if (r->staged && r->kind == kOut && r->bytes)
+      IK_HIP(hipMemcpyAsync(r->user, r->dev, r->bytes, hipMemcpyDeviceToHost, c_->stream));
+  return IK_OK;
+}
+
 int set_dev(ik_ctx *c) {
   IK_HIP(hipSetDevice(c->device));
+  return IK_OK;
+}
+
+int check_flags(const char *who, int flags, const void *ang) {
+  if ((flags & IK_F_ASYNC) && !(flags & IK_F_DEVICE))
+    return fail(IK_E_BADARG, std::string(who) + ": IK_F_ASYNC requires IK_F_DEVICE");
+  if ((flags & IK_F_DEVICE) && (reinterpret_cast<uintptr_t>(ang) & 15))
+    return fail(IK_E_BADARG, std::string(who) + ": device ang must be 16-byte aligned");
   return IK_OK;
 }
 
@@ -499,52 +536,33 @@ int ik_stats_fetch(ik_ctx *c, ik_stats *stats) {
 
 int ik_check_limits(ik_ctx *c, const double *pts, int64_t n, int flags, ik_stats *stats) {
   if (!c || n < 0 || (n > 0 && !pts)) return fail(IK_E_BADARG, "ik_check_limits: bad args");
-  if ((flags & IK_F_ASYNC) && !(flags & IK_F_DEVICE))
-    return fail(IK_E_BADARG, "IK_F_ASYNC requires IK_F_DEVICE");
-  int rc = set_dev(c);
-  if (rc) return rc;
+  int rc = check_flags("ik_check_limits", flags);
+  if (rc || (rc = set_dev(c))) return rc;
   KtScope kts(c);
-  const double *dp = pts;
-  if (!(flags & IK_F_DEVICE)) {
-    if ((rc = ensure_scratch(c, (size_t)n * 24 + 256))) return rc;
-    IK_HIP(hipMemcpyAsync(c->scratch, pts, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
-    dp = static_cast<const double *>(c->scratch);
-  }
+  Stage st(c, flags);
+  const int r_pts = st.in(pts, (size_t)n * 24);
+  if ((rc = st.reserve())) return rc;
   launch_reset_stats(c->d_stats, c->stream);
-  launch_check_limits(c->robot, dp, n, c->d_stats, c->stream);
+  launch_check_limits(c->robot, st.at<const double>(r_pts), n, c->d_stats, c->stream);
   IK_HIP(hipGetLastError());
   return finish(c, flags, stats);
 }
 
 int ik_fk(ik_ctx *c, const double *ang, int64_t n, double *xyz, double *mats, int flags,
           ik_stats *stats) {
-  double *joints = mats;  // n x 4 x 16
   if (!c || n < 0 || (n > 0 && (!ang || !xyz))) return fail(IK_E_BADARG, "ik_fk: bad args");
-  if ((flags & IK_F_ASYNC) && !(flags & IK_F_DEVICE))
-    return fail(IK_E_BADARG, "IK_F_ASYNC requires IK_F_DEVICE");
-  int rc = set_dev(c);
-  if (rc) return rc;
+  int rc = check_flags("ik_fk", flags);
+  if (rc || (rc = set_dev(c))) return rc;
   KtScope kts(c);
-  const double *da = ang;
-  double *dx = xyz, *dj = joints;
-  if (!(flags & IK_F_DEVICE)) {
-    size_t b_in = Stage::up((size_t)n * 32), b_x = Stage::up((size_t)n * 24),
-           b_j = joints ? Stage::up((size_t)n * 512) : 0;
-    if ((rc = ensure_scratch(c, b_in + b_x + b_j))) return rc;
-    char *s = static_cast<char *>(c->scratch);
-    IK_HIP(hipMemcpyAsync(s, ang, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-    da = reinterpret_cast<double *>(s);
-    dx = reinterpret_cast<double *>(s + b_in);
-    dj = joints ? reinterpret_cast<double *>(s + b_in + b_x) : nullptr;
-  }
+  Stage st(c, flags);
+  const int r_ang = st.in(ang, (size_t)n * 32), r_xyz = st.out(xyz, (size_t)n * 24),
+            r_mats = st.out(mats, (size_t)n * 512);  // n x 4 x 16
+  if ((rc = st.reserve())) return rc;
   launch_reset_stats(c->d_stats, c->stream);
-  launch_fk(c->robot, da, n, dx, dj, c->d_stats, c->stream);
+  launch_fk(c->robot, st.at<const double>(r_ang), n, st.at<double>(r_xyz),
+            st.at<double>(r_mats), c->d_stats, c->stream);
   IK_HIP(hipGetLastError());
-  if (!(flags & IK_F_DEVICE) && n > 0) {
-    IK_HIP(hipMemcpyAsync(xyz, dx, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream));
-    if (joints)
-      IK_HIP(hipMemcpyAsync(joints, dj, (size_t)n * 512, hipMemcpyDeviceToHost, c->stream));
-  }
+  if ((rc = st.flush())) return rc;
   return finish(c, flags, stats);
 }
 
@@ -553,38 +571,18 @@ int ik_fk_chain(ik_ctx *c, int nj, const double *dh, const double *ang, int64_t 
   if (!c || nj < 2 || nj > kFkMaxJoints || !dh || n < 0 || (n > 0 && (!ang || !xyz)))
     return fail(IK_E_BADARG, "ik_fk_chain: bad args (nj must be 2.." +
                                  std::to_string(kFkMaxJoints) + ")");
-  if ((flags & IK_F_ASYNC) && !(flags & IK_F_DEVICE))
-    return fail(IK_E_BADARG, "IK_F_ASYNC requires IK_F_DEVICE");
-  int rc = set_dev(c);
-  if (rc) return rc;
+  int rc = check_flags("ik_fk_chain", flags);
+  if (rc || (rc = set_dev(c))) return rc;
   KtScope kts(c);
-  const bool dev = flags & IK_F_DEVICE;
-  const size_t b_dh = Stage::up((size_t)nj * 32);
-  const size_t b_in = dev ? 0 : Stage::up((size_t)n * nj * 8);
-  const size_t b_x = dev ? 0 : Stage::up((size_t)n * 24);
-  const size_t b_m = (dev || !mats) ? 0 : Stage::up((size_t)n * nj * 128);
-  if ((rc = ensure_scratch(c, b_dh + b_in + b_x + b_m))) return rc;
-  char *s = static_cast<char *>(c->scratch);
-  // the DH table always travels from host memory
-  IK_HIP(hipMemcpyAsync(s, dh, (size_t)nj * 32, hipMemcpyHostToDevice, c->stream));
-  const double *dd = reinterpret_cast<const double *>(s);
-  const double *da = ang;
-  double *dx = xyz, *dm = mats;
-  if (!dev) {
-    char *q = s + b_dh;
-    IK_HIP(hipMemcpyAsync(q, ang, (size_t)n * nj * 8, hipMemcpyHostToDevice, c->stream));
-    da = reinterpret_cast<const double *>(q);
-    dx = reinterpret_cast<double *>(q + b_in);
-    dm = mats ? reinterpret_cast<double *>(q + b_in + b_x) : nullptr;
-  }
+  Stage st(c, flags);
+  const int r_dh = st.table(dh, (size_t)nj * 32), r_ang = st.in(ang, (size_t)n * nj * 8),
+            r_xyz = st.out(xyz, (size_t)n * 24), r_mats = st.out(mats, (size_t)n * nj * 128);
+  if ((rc = st.reserve())) return rc;
   launch_reset_stats(c->d_stats, c->stream);
-  launch_fk_n(nj, dd, da, n, dx, dm, c->d_stats, c->stream);
+  launch_fk_n(nj, st.at<const double>(r_dh), st.at<const double>(r_ang), n, st.at<double>(r_xyz),
+              st.at<double>(r_mats), c->d_stats, c->stream);
   IK_HIP(hipGetLastError());
-  if (!dev && n > 0) {
-    IK_HIP(hipMemcpyAsync(xyz, dx, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream));
-    if (mats)
-      IK_HIP(hipMemcpyAsync(mats, dm, (size_t)n * nj * 128, hipMemcpyDeviceToHost, c->stream));
-  }
+  if ((rc = st.flush())) return rc;
   // dh came from a host buffer that may go away: always complete before return
   if (flags & IK_F_ASYNC) IK_HIP(hipStreamSynchronize(c->stream));
   return finish(c, flags, stats);
@@ -600,53 +598,21 @@ int ik_fabrik_solve_fk(ik_ctx *c, const double *pts, int64_t n, double tol, int3
                        ik_stats *stats) {
   if (!c || n < 0 || (n > 0 && (!pts || !ang)) || max_iter < 0)
     return fail(IK_E_BADARG, "ik_fabrik_solve: bad args");
-  if ((flags & IK_F_ASYNC) && !(flags & IK_F_DEVICE))
-    return fail(IK_E_BADARG, "IK_F_ASYNC requires IK_F_DEVICE");
-  if ((flags & IK_F_DEVICE) && (reinterpret_cast<uintptr_t>(ang) & 15))
-    return fail(IK_E_BADARG, "ik_fabrik_solve: device ang must be 16-byte aligned");
-  int rc = set_dev(c);
-  if (rc) return rc;
+  int rc = check_flags("ik_fabrik_solve", flags, ang);
+  if (rc || (rc = set_dev(c))) return rc;
   KtScope kts(c);
-  const bool dev = flags & IK_F_DEVICE;
-  if (!dev && pipeline_wanted(c, n, {pts, ang, iters, joints, fk_err}))
+  if (!(flags & IK_F_DEVICE) && pipeline_wanted(c, n, {pts, ang, iters, joints, fk_err}))
     return fabrik_host_pipeline(c, pts, n, tol, max_iter, ang, iters, joints, fk_err, flags,
                                 stats);
-  size_t b_work = Stage::up(fabrik_scratch_bytes(n));
-  size_t b_in = dev ? 0 : Stage::up((size_t)n * 24);
-  size_t b_ang = dev ? 0 : Stage::up((size_t)n * 32);
-  size_t b_it = (dev || !iters) ? 0 : Stage::up((size_t)n * 4);
-  size_t b_jo = (dev || !joints) ? 0 : Stage::up((size_t)n * 96);
-  size_t b_fe = (dev || !fk_err) ? 0 : Stage::up((size_t)n * 8);
-  if ((rc = ensure_scratch(c, b_work + b_in + b_ang + b_it + b_jo + b_fe))) return rc;
-  char *s = static_cast<char *>(c->scratch);
-  void *work = s;
-  const double *dp = pts;
-  double *da = ang, *dj = joints, *dfe = fk_err;
-  int32_t *di = iters;
-  if (!dev) {
-    char *q = s + b_work;
-    dp = reinterpret_cast<double *>(q);
-    IK_HIP(hipMemcpyAsync(q, pts, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
-    q += b_in;
-    da = reinterpret_cast<double *>(q);
-    q += b_ang;
-    di = iters ? reinterpret_cast<int32_t *>(q) : nullptr;
-    q += b_it;
-    dj = joints ? reinterpret_cast<double *>(q) : nullptr;
-    q += b_jo;
-    dfe = fk_err ? reinterpret_cast<double *>(q) : nullptr;
-  }
-  rc = fabrik_launch(c, dp, n, tol, max_iter, da, di, dj, dfe, !(flags & IK_F_NO_LIMITS), work);
-  if (rc) return rc;
-  if (!dev && n > 0) {
-    IK_HIP(hipMemcpyAsync(ang, da, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-    if (iters)
-      IK_HIP(hipMemcpyAsync(iters, di, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (joints)
-      IK_HIP(hipMemcpyAsync(joints, dj, (size_t)n * 96, hipMemcpyDeviceToHost, c->stream));
-    if (fk_err)
-      IK_HIP(hipMemcpyAsync(fk_err, dfe, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  }
+  Stage st(c, flags);
+  const int r_work = st.work(fabrik_scratch_bytes(n)), r_pts = st.in(pts, (size_t)n * 24),
+            r_ang = st.out(ang, (size_t)n * 32), r_it = st.out(iters, (size_t)n * 4),
+            r_jo = st.out(joints, (size_t)n * 96), r_fe = st.out(fk_err, (size_t)n * 8);
+  if ((rc = st.reserve())) return rc;
+  rc = fabrik_launch(c, st.at<const double>(r_pts), n, tol, max_iter, st.at<double>(r_ang),
+                     st.at<int32_t>(r_it), st.at<double>(r_jo), st.at<double>(r_fe),
+                     !(flags & IK_F_NO_LIMITS), st.at<void>(r_work));
+  if (rc || (rc = st.flush())) return rc;
   return finish(c, flags, stats);
 }
 
@@ -696,47 +662,21 @@ int ik_fabrik_calc(ik_ctx *c, int nj, const double *dists, const double *init,
       (n > 0 && (!init || !goals || !joints)) || max_iter < 0)
     return fail(IK_E_BADARG, "ik_fabrik_calc: bad args (nj must be 1.." +
                                  std::to_string(kCalcMaxJoints) + ")");
-  if ((flags & IK_F_ASYNC) && !(flags & IK_F_DEVICE))
-    return fail(IK_E_BADARG, "IK_F_ASYNC requires IK_F_DEVICE");
-  int rc = set_dev(c);
-  if (rc) return rc;
+  int rc = check_flags("ik_fabrik_calc", flags);
+  if (rc || (rc = set_dev(c))) return rc;
   KtScope kts(c);
-  const bool dev = flags & IK_F_DEVICE;
-  size_t b_d = Stage::up((size_t)nj * 8);
-  size_t n_init = init_shared ? (size_t)nj * 3 : (size_t)n * nj * 3;
-  size_t b_init = dev ? 0 : Stage::up(n_init * 8);
-  size_t b_g = dev ? 0 : Stage::up((size_t)n * 24);
-  size_t b_jo = dev ? 0 : Stage::up((size_t)n * nj * 24);
-  size_t b_it = (dev || !iters) ? 0 : Stage::up((size_t)n * 4);
-  if ((rc = ensure_scratch(c, b_d + b_init + b_g + b_jo + b_it))) return rc;
-  char *s = static_cast<char *>(c->scratch);
-  // the link distances always travel from host memory
-  IK_HIP(hipMemcpyAsync(s, dists, (size_t)nj * 8, hipMemcpyHostToDevice, c->stream));
-  const double *dd = reinterpret_cast<double *>(s);
-  const double *di = init, *dg = goals;
-  double *djo = joints;
-  int32_t *dit = iters;
-  if (!dev) {
-    char *q = s + b_d;
-    IK_HIP(hipMemcpyAsync(q, init, n_init * 8, hipMemcpyHostToDevice, c->stream));
-    di = reinterpret_cast<double *>(q);
-    q += b_init;
-    IK_HIP(hipMemcpyAsync(q, goals, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
-    dg = reinterpret_cast<double *>(q);
-    q += b_g;
-    djo = reinterpret_cast<double *>(q);
-    q += b_jo;
-    dit = iters ? reinterpret_cast<int32_t *>(q) : nullptr;
-  }
+  Stage st(c, flags);
+  const size_t n_init = init_shared ? (size_t)nj * 3 : (size_t)n * nj * 3;
+  const int r_d = st.table(dists, (size_t)nj * 8), r_init = st.in(init, n_init * 8),
+            r_g = st.in(goals, (size_t)n * 24), r_jo = st.out(joints, (size_t)n * nj * 24),
+            r_it = st.out(iters, (size_t)n * 4);
+  if ((rc = st.reserve())) return rc;
   launch_reset_stats(c->d_stats, c->stream);
-  launch_fabrik_calc(nj, dd, di, init_shared != 0, dg, n, tol, max_iter, djo, dit, c->d_stats,
-                     c->stream);
+  launch_fabrik_calc(nj, st.at<const double>(r_d), st.at<const double>(r_init), init_shared != 0,
+                     st.at<const double>(r_g), n, tol, max_iter, st.at<double>(r_jo),
+                     st.at<int32_t>(r_it), c->d_stats, c->stream);
   IK_HIP(hipGetLastError());
-  if (!dev && n > 0) {
-    IK_HIP(hipMemcpyAsync(joints, djo, (size_t)n * nj * 24, hipMemcpyDeviceToHost, c->stream));
-    if (iters)
-      IK_HIP(hipMemcpyAsync(iters, dit, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  }
+  if ((rc = st.flush())) return rc;
   // dists came from a host buffer that may go away: always complete before return
   if (flags & IK_F_ASYNC) IK_HIP(hipStreamSynchronize(c->stream));
   return finish(c, flags, stats);
@@ -941,37 +881,19 @@ int ik_ann_solve(ik_ctx *c, const double *pts, int64_t n, float *ang, double *fk
                  int flags, ik_stats *stats) {
   if (!c || n < 0 || (n > 0 && (!pts || !ang))) return fail(IK_E_BADARG, "ik_ann_solve: bad args");
   if (!c->ann_loaded) return fail(IK_E_NOMODEL, "ik_ann_solve: no model loaded (ik_ann_load)");
-  if ((flags & IK_F_ASYNC) && !(flags & IK_F_DEVICE))
-    return fail(IK_E_BADARG, "IK_F_ASYNC requires IK_F_DEVICE");
-  if ((flags & IK_F_DEVICE) && (reinterpret_cast<uintptr_t>(ang) & 15))
-    return fail(IK_E_BADARG, "ik_ann_solve: device ang must be 16-byte aligned");
-  int rc = set_dev(c);
-  if (rc) return rc;
+  int rc = check_flags("ik_ann_solve", flags, ang);
+  if (rc || (rc = set_dev(c))) return rc;
   KtScope kts(c);
-  const bool dev = flags & IK_F_DEVICE;
   // (no chunked pipeline for ANN: its copies are ~2 % of the call and splitting
   // the launch into chunks costs more tile-quantisation tail than the overlap
   // saves -- 41.6 vs 41.1 ms per 1M points measured)
-  const double *dp = pts;
-  float *da = ang;
-  double *de = fk_err;
-  if (!dev) {
-    size_t b_in = Stage::up((size_t)n * 24), b_a = Stage::up((size_t)n * 16),
-           b_e = fk_err ? Stage::up((size_t)n * 8) : 0;
-    if ((rc = ensure_scratch(c, b_in + b_a + b_e))) return rc;
-    char *s = static_cast<char *>(c->scratch);
-    IK_HIP(hipMemcpyAsync(s, pts, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
-    dp = reinterpret_cast<double *>(s);
-    da = reinterpret_cast<float *>(s + b_in);
-    de = fk_err ? reinterpret_cast<double *>(s + b_in + b_a) : nullptr;
-  }
-  rc = ann_launch(c, dp, n, da, de, !(flags & IK_F_NO_LIMITS));
-  if (rc) return rc;
-  if (!dev && n > 0) {
-    IK_HIP(hipMemcpyAsync(ang, da, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    if (fk_err)
-      IK_HIP(hipMemcpyAsync(fk_err, de, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  }
+  Stage st(c, flags);
+  const int r_pts = st.in(pts, (size_t)n * 24), r_ang = st.out(ang, (size_t)n * 16),
+            r_fe = st.out(fk_err, (size_t)n * 8);
+  if ((rc = st.reserve())) return rc;
+  rc = ann_launch(c, st.at<const double>(r_pts), n, st.at<float>(r_ang), st.at<double>(r_fe),
+                  !(flags & IK_F_NO_LIMITS));
+  if (rc || (rc = st.flush())) return rc;
   return finish(c, flags, stats);
 }
 
@@ -983,53 +905,26 @@ static int refine_args(const char *who, ik_ctx *c, int64_t n, bool arrays, doubl
   if (std::isnan(tol)) return fail(IK_E_BADARG, w + ": tol is NaN");
   if (!std::isfinite(damping) || !(damping > 0.0))
     return fail(IK_E_BADARG, w + ": damping must be finite and > 0");
-  if ((flags & IK_F_ASYNC) && !(flags & IK_F_DEVICE))
-    return fail(IK_E_BADARG, "IK_F_ASYNC requires IK_F_DEVICE");
-  if ((flags & IK_F_DEVICE) && (reinterpret_cast<uintptr_t>(ang) & 15))
-    return fail(IK_E_BADARG, w + ": device ang must be 16-byte aligned");
-  return IK_OK;
+  return check_flags(who, flags, ang);
 }
 
 int ik_refine(ik_ctx *c, const double *pts, const double *seed, int64_t n, double tol,
               int32_t max_iter, double damping, double *ang, int32_t *iters, double *fk_err,
               int flags, ik_stats *stats) {
   int rc = refine_args("ik_refine", c, n, pts && seed && ang, tol, max_iter, damping, ang, flags);
-  if (rc) return rc;
-  if ((rc = set_dev(c))) return rc;
+  if (rc || (rc = set_dev(c))) return rc;
   KtScope kts(c);
-  const bool dev = flags & IK_F_DEVICE;
-  const double *dp = pts, *ds = seed;
-  double *da = ang, *dfe = fk_err;
-  int32_t *di = iters;
-  if (!dev) {
-    const size_t b_in = Stage::up((size_t)n * 24), b_sd = Stage::up((size_t)n * 32),
-                 b_ang = Stage::up((size_t)n * 32), b_it = iters ? Stage::up((size_t)n * 4) : 0,
-                 b_fe = fk_err ? Stage::up((size_t)n * 8) : 0;
-    if ((rc = ensure_scratch(c, b_in + b_sd + b_ang + b_it + b_fe))) return rc;
-    char *q = static_cast<char *>(c->scratch);
-    IK_HIP(hipMemcpyAsync(q, pts, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
-    dp = reinterpret_cast<double *>(q);
-    q += b_in;
-    IK_HIP(hipMemcpyAsync(q, seed, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-    ds = reinterpret_cast<double *>(q);
-    q += b_sd;
-    da = reinterpret_cast<double *>(q);
-    q += b_ang;
-    di = iters ? reinterpret_cast<int32_t *>(q) : nullptr;
-    q += b_it;
-    dfe = fk_err ? reinterpret_cast<double *>(q) : nullptr;
-  }
+  Stage st(c, flags);
+  const int r_pts = st.in(pts, (size_t)n * 24), r_seed = st.in(seed, (size_t)n * 32),
+            r_ang = st.out(ang, (size_t)n * 32), r_it = st.out(iters, (size_t)n * 4),
+            r_fe = st.out(fk_err, (size_t)n * 8);
+  if ((rc = st.reserve())) return rc;
   launch_reset_stats(c->d_stats, c->stream);
-  launch_refine(c->rconst, dp, ds, n, tol, max_iter, damping, da, di, dfe,
-                !(flags & IK_F_NO_LIMITS), c->d_stats, c->stream);
+  launch_refine(c->rconst, st.at<const double>(r_pts), st.at<const double>(r_seed), n, tol,
+                max_iter, damping, st.at<double>(r_ang), st.at<int32_t>(r_it),
+                st.at<double>(r_fe), !(flags & IK_F_NO_LIMITS), c->d_stats, c->stream);
   IK_HIP(hipGetLastError());
-  if (!dev && n > 0) {
-    IK_HIP(hipMemcpyAsync(ang, da, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-    if (iters)
-      IK_HIP(hipMemcpyAsync(iters, di, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (fk_err)
-      IK_HIP(hipMemcpyAsync(fk_err, dfe, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  }
+  if ((rc = st.flush())) return rc;
   return finish(c, flags, stats);
 }
 
@@ -1043,49 +938,22 @@ int ik_ann_solve_refined(ik_ctx *c, const double *pts, int64_t n, double tol, in
     return fail(IK_E_NOMODEL, "ik_ann_solve_refined: no model loaded (ik_ann_load)");
   if ((rc = set_dev(c))) return rc;
   KtScope kts(c);
-  const bool dev = flags & IK_F_DEVICE;
   const bool limits = !(flags & IK_F_NO_LIMITS);
+  Stage st(c, flags);
   // the network's float32 angles never leave the device: they are the refine's seeds
-  const size_t b_seed = Stage::up((size_t)n * 16);
-  const size_t b_in = dev ? 0 : Stage::up((size_t)n * 24);
-  const size_t b_ang = dev ? 0 : Stage::up((size_t)n * 32);
-  const size_t b_it = (dev || !iters) ? 0 : Stage::up((size_t)n * 4);
-  const size_t b_fe = (dev || !fk_err) ? 0 : Stage::up((size_t)n * 8);
-  const size_t b_se = (dev || !seed_fk_err) ? 0 : Stage::up((size_t)n * 8);
-  if ((rc = ensure_scratch(c, b_seed + b_in + b_ang + b_it + b_fe + b_se))) return rc;
-  char *q = static_cast<char *>(c->scratch);
-  float *dseed = reinterpret_cast<float *>(q);
-  q += b_seed;
-  const double *dp = pts;
-  double *da = ang, *dfe = fk_err, *dse = seed_fk_err;
-  int32_t *di = iters;
-  if (!dev) {
-    IK_HIP(hipMemcpyAsync(q, pts, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
-    dp = reinterpret_cast<double *>(q);
-    q += b_in;
-    da = reinterpret_cast<double *>(q);
-    q += b_ang;
-    di = iters ? reinterpret_cast<int32_t *>(q) : nullptr;
-    q += b_it;
-    dfe = fk_err ? reinterpret_cast<double *>(q) : nullptr;
-    q += b_fe;
-    dse = seed_fk_err ? reinterpret_cast<double *>(q) : nullptr;
-  }
-  if ((rc = ann_launch(c, dp, n, dseed, dse, limits))) return rc;
+  const int r_seed = st.work((size_t)n * 16), r_pts = st.in(pts, (size_t)n * 24),
+            r_ang = st.out(ang, (size_t)n * 32), r_it = st.out(iters, (size_t)n * 4),
+            r_fe = st.out(fk_err, (size_t)n * 8), r_se = st.out(seed_fk_err, (size_t)n * 8);
+  if ((rc = st.reserve())) return rc;
+  const double *dp = st.at<const double>(r_pts);
+  float *dseed = st.at<float>(r_seed);
+  if ((rc = ann_launch(c, dp, n, dseed, st.at<double>(r_se), limits))) return rc;
   // the call's stats are the refined result's
   launch_reset_stats(c->d_stats, c->stream);
-  launch_refine_f32(c->rconst, dp, dseed, n, tol, max_iter, damping, da, di, dfe, limits,
-                    c->d_stats, c->stream);
+  launch_refine_f32(c->rconst, dp, dseed, n, tol, max_iter, damping, st.at<double>(r_ang),
+                    st.at<int32_t>(r_it), st.at<double>(r_fe), limits, c->d_stats, c->stream);
   IK_HIP(hipGetLastError());
-  if (!dev && n > 0) {
-    IK_HIP(hipMemcpyAsync(ang, da, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-    if (iters)
-      IK_HIP(hipMemcpyAsync(iters, di, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (fk_err)
-      IK_HIP(hipMemcpyAsync(fk_err, dfe, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (seed_fk_err)
-      IK_HIP(hipMemcpyAsync(seed_fk_err, dse, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  }
+  if ((rc = st.flush())) return rc;
   return finish(c, flags, stats);
 }
 

@@ -1,6 +1,7 @@
 // ik_internal.h -- the context behind the C ABI and the helpers its
-// translation units share (ik_api.cpp: single-device calls; ik_comm.cpp: the
-// RCCL-sharded calls).  Not installed; include/ikhip.h is the interface.
+// translation units share (ik_api.cpp: single-device calls; ik_pipe.cpp: the
+// chunked host-pointer pipeline; ik_shard.hip: the RCCL-sharded calls).  Not
+// installed; include/ikhip.h is the interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -157,12 +158,65 @@ struct KtScope {
   ik_ctx *c_;
 };
 
-struct Stage {
+// One call's regions of the context's scratch, in the order they are described,
+// each on a 256-byte boundary (the kernels store double2 / float4).  Describe
+// the regions, reserve() -- the scratch may be reallocated until then -- take
+// the device pointers with at(), launch, flush().  Host pointers (no
+// IK_F_DEVICE): inputs and present outputs are staged, copied in by reserve()
+// and out by flush(), in order.  Device pointers: at() is the caller's own.
+// Every copy is asynchronous on the context's stream and nothing here waits
+// (finish() does).
+class Stage {
+ public:
   static size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
+  // The layout alone: add a region, get its offset, know the total.
+  struct Carve {
+    size_t total = 0;
+    size_t add(size_t bytes) {
+      const size_t at = total;
+      total += up(bytes);
+      return at;
+    }
+  };
+
+  Stage(ik_ctx *c, int flags) : c_(c), dev_(flags & IK_F_DEVICE) {}
+  // Each returns the region's handle for at().
+  int work(size_t bytes) { return add(kWork, nullptr, bytes); }  // device-only, both modes
+  // host memory in both modes (the call completes before it returns)
+  int table(const void *host, size_t bytes) { return add(kTable, host, bytes); }
+  int in(const void *p, size_t bytes) { return add(kIn, p, bytes); }
+  // p null: an absent output -- no scratch, a null device pointer, no copy
+  int out(void *p, size_t bytes) { return add(kOut, p, bytes); }
+  int reserve();  // grows the scratch (once), then queues the host -> device copies
+  int flush();    // after the kernels: queues the device -> host copies
+  template <class T>
+  T *at(int r) const {
+    return static_cast<T *>(r_[r].dev);
+  }
+
+ private:
+  enum Kind { kWork, kTable, kIn, kOut };
+  struct Region {
+    Kind kind;
+    void *user;  // the caller's pointer
+    size_t bytes, off;
+    bool staged;  // lives in the scratch at `off`
+    void *dev;
+  };
+  static constexpr int kMax = 6;  // (ik_ann_solve_refined)
+  int add(Kind kind, const void *user, size_t bytes);
+  ik_ctx *c_;
+  bool dev_;
+  Carve cv_;
+  int n_ = 0;
+  Region r_[kMax];
 };
 
 int ensure_scratch(ik_ctx *c, size_t bytes);
 int set_dev(ik_ctx *c);
+// The refusals every enqueueing call shares: IK_F_ASYNC needs IK_F_DEVICE, and a
+// device `ang` (null: the call has none) is stored 16 bytes at a time.
+int check_flags(const char *who, int flags, const void *ang = nullptr);
 void stats_from_dev(const ikhip::DevStats &d, ik_stats *s);
 int finish(ik_ctx *c, int flags, ik_stats *stats);
 // Device pointers only, on the context's stream: stats reset + the solve's kernels.

@@ -186,26 +186,24 @@ int fabrik_host_pipeline(ik_ctx *c, const double *pts, int64_t n, double tol, in
   const int K = chunks_for(n);
   int64_t begin[kPipeMaxChunks + 1];
   for (int k = 0; k <= K; ++k) begin[k] = n * k / K;
-  const size_t b_pts = Stage::up((size_t)n * 24), b_ang = Stage::up((size_t)n * 32);
-  const size_t b_it = iters ? Stage::up((size_t)n * 4) : 0;
-  const size_t b_jo = joints ? Stage::up((size_t)n * 96) : 0;
-  const size_t b_fe = fk_err ? Stage::up((size_t)n * 8) : 0;
-  const size_t b_work = Stage::up(fabrik_scratch_bytes(begin[1] + 1));  // chunks differ by <= 1
-  int rc = pipe_ready(c, b_pts + b_ang + b_it + b_jo + b_fe + b_work);
+  // the points, then every present output region (n rows each), then the work buffer
+  Region outs[4] = {{32, reinterpret_cast<char *>(ang), nullptr},
+                    {4, reinterpret_cast<char *>(iters), nullptr},
+                    {96, reinterpret_cast<char *>(joints), nullptr},
+                    {8, reinterpret_cast<char *>(fk_err), nullptr}};
+  Stage::Carve cv;
+  const size_t o_pts = cv.add((size_t)n * 24);
+  size_t o_out[4] = {};
+  for (int r = 0; r < 4; ++r)
+    if (outs[r].host) o_out[r] = cv.add((size_t)n * outs[r].row);
+  const size_t o_work = cv.add(fabrik_scratch_bytes(begin[1] + 1));  // chunks differ by <= 1
+  int rc = pipe_ready(c, cv.total);
   if (rc) return rc;
-  char *q = static_cast<char *>(c->pipe.buf);
-  double *d_pts = reinterpret_cast<double *>(q);
-  q += b_pts;
-  Region outs[4] = {{32, reinterpret_cast<char *>(ang), q}, {4, nullptr, nullptr},
-                    {96, nullptr, nullptr}, {8, nullptr, nullptr}};
-  q += b_ang;
-  if (iters) outs[1] = {4, reinterpret_cast<char *>(iters), q};
-  q += b_it;
-  if (joints) outs[2] = {96, reinterpret_cast<char *>(joints), q};
-  q += b_jo;
-  if (fk_err) outs[3] = {8, reinterpret_cast<char *>(fk_err), q};
-  q += b_fe;
-  void *work = q;
+  char *buf = static_cast<char *>(c->pipe.buf);
+  double *d_pts = reinterpret_cast<double *>(buf + o_pts);
+  for (int r = 0; r < 4; ++r)
+    if (outs[r].host) outs[r].dev = buf + o_out[r];
+  void *work = buf + o_work;
   const bool limits = !(flags & IK_F_NO_LIMITS);
   rc = run_chunks(c, K, begin, pts, d_pts, outs, 4, [&](int k, int64_t b, int64_t m) {
     return fabrik_launch(

@@ -1015,9 +1015,9 @@ int ik_fk_err_quantile(ik_ctx *c, double q, double *out) {
 static int sharded_common(ik_ctx *c, int flags, const char *who) {
   if (!c) return fail(IK_E_BADARG, std::string(who) + ": NULL context");
   if (!c->comm.comm) return fail(IK_E_BADARG, std::string(who) + ": no communicator (ik_comm_init)");
-  if ((flags & IK_F_ASYNC) && !(flags & IK_F_DEVICE))
-    return fail(IK_E_BADARG, "IK_F_ASYNC requires IK_F_DEVICE");
-  return set_dev(c);
+  // (the callers check their arrays next, then `ang` with check_flags again)
+  const int rc = check_flags(who, flags);
+  return rc ? rc : set_dev(c);
 }
 
 // Host pointers: device scratch holds the points (the rank's parts, at their
@@ -1026,25 +1026,20 @@ struct HostStage {
   char *pts, *out[2], *fk;
 };
 
-static int host_stage(ik_ctx *c, const ik_shard_plan &P, int64_t n, const int *rb, int nreg,
-                      bool fk, size_t extra, HostStage *h, char **extra_at) {
-  const size_t b_pts = Stage::up((size_t)n * 24);
-  size_t b_out[2] = {0, 0};
-  for (int q = 0; q < nreg; ++q) b_out[q] = Stage::up((size_t)n * rb[q]);
-  const size_t b_fk = fk ? Stage::up((size_t)n * 8) : 0;
-  int rc = ensure_scratch(c, extra + b_pts + b_out[0] + b_out[1] + b_fk);
+static int host_stage(ik_ctx *c, int64_t n, const int *rb, int nreg, bool fk, size_t extra,
+                      HostStage *h, char **extra_at) {
+  Stage::Carve cv;
+  const size_t o_extra = cv.add(extra), o_pts = cv.add((size_t)n * 24);
+  size_t o_out[2] = {0, 0};
+  for (int q = 0; q < nreg; ++q) o_out[q] = cv.add((size_t)n * rb[q]);
+  const size_t o_fk = fk ? cv.add((size_t)n * 8) : 0;
+  int rc = ensure_scratch(c, cv.total);
   if (rc) return rc;
   char *s = static_cast<char *>(c->scratch);
-  *extra_at = s;
-  s += extra;
-  h->pts = s;
-  s += b_pts;
-  for (int q = 0; q < 2; ++q) {
-    h->out[q] = q < nreg ? s : nullptr;
-    s += b_out[q];
-  }
-  h->fk = fk ? s : nullptr;
-  (void)P;
+  *extra_at = s + o_extra;
+  h->pts = s + o_pts;
+  for (int q = 0; q < 2; ++q) h->out[q] = q < nreg ? s + o_out[q] : nullptr;
+  h->fk = fk ? s + o_fk : nullptr;
   return IK_OK;
 }
 
@@ -1084,8 +1079,7 @@ int ik_ann_solve_sharded(ik_ctx *c, const double *pts, int64_t n, float *ang, do
   if (rc) return rc;
   if (n < 0 || n >= ((int64_t)1 << 48) || (n > 0 && (!pts || !ang)))
     return fail(IK_E_BADARG, "ik_ann_solve_sharded: bad args");
-  if ((flags & IK_F_DEVICE) && (reinterpret_cast<uintptr_t>(ang) & 15))
-    return fail(IK_E_BADARG, "ik_ann_solve_sharded: device ang must be 16-byte aligned");
+  if ((rc = check_flags("ik_ann_solve_sharded", flags, ang))) return rc;
   if (!c->ann_loaded) return fail(IK_E_NOMODEL, "ik_ann_solve_sharded: no model loaded");
   KtScope kts(c);
   const bool dev = flags & IK_F_DEVICE;
@@ -1108,7 +1102,7 @@ int ik_ann_solve_sharded(ik_ctx *c, const double *pts, int64_t n, float *ang, do
       return rc;
     const int rb[1] = {16};
     char *unused = nullptr;
-    if ((rc = host_stage(c, P, n, rb, 1, fk_err != nullptr, 0, &hs, &unused))) return rc;
+    if ((rc = host_stage(c, n, rb, 1, fk_err != nullptr, 0, &hs, &unused))) return rc;
     if ((rc = host_points_in(c, P, pts, hs.pts))) return rc;
     dp = reinterpret_cast<const double *>(hs.pts);
     R[0].out = hs.out[0];
@@ -1138,8 +1132,7 @@ int ik_fabrik_solve_sharded(ik_ctx *c, const double *pts, int64_t n, double tol,
   if (rc) return rc;
   if (n < 0 || n >= ((int64_t)1 << 48) || (n > 0 && (!pts || !ang)) || max_iter < 0)
     return fail(IK_E_BADARG, "ik_fabrik_solve_sharded: bad args");
-  if ((flags & IK_F_DEVICE) && (reinterpret_cast<uintptr_t>(ang) & 15))
-    return fail(IK_E_BADARG, "ik_fabrik_solve_sharded: device ang must be 16-byte aligned");
+  if ((rc = check_flags("ik_fabrik_solve_sharded", flags, ang))) return rc;
   KtScope kts(c);
   const bool dev = flags & IK_F_DEVICE;
   const int g = c->comm.nranks;
@@ -1165,7 +1158,7 @@ int ik_fabrik_solve_sharded(ik_ctx *c, const double *pts, int64_t n, double tol,
     if (c->comm.ev_end_set && (rc = comm_wait(c, c->comm.ev_end, "the previous sharded call")))
       return rc;
     const int rb[2] = {32, 4};
-    if ((rc = host_stage(c, P, n, rb, nreg, fk_err != nullptr, b_work, &hs, &work))) return rc;
+    if ((rc = host_stage(c, n, rb, nreg, fk_err != nullptr, b_work, &hs, &work))) return rc;
     if ((rc = host_points_in(c, P, pts, hs.pts))) return rc;
     dp = reinterpret_cast<const double *>(hs.pts);
     R[0].out = hs.out[0];
