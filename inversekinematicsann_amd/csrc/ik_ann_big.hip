@@ -537,45 +537,6 @@ int64_t ann_big_rows(const AnnBigModel &m, size_t act_bytes) {
 // (annb_gemm_kernel's buffer offsets are 32-bit: a panel's A is at most 128 rows of
 // 16384 floats, 8 MiB, and a block's weights 4 tiles x 2048 groups x 1 KiB, 8 MiB)
 
-// (host) round to nearest even, as v_cvt_pk_bf16_f32 does on the device
-static uint16_t bf16_rne_h(float x) {
-  uint32_t u;
-  std::memcpy(&u, &x, 4);
-  if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)(u >> 16);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static float bf16_f32_h(uint16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float x;
-  std::memcpy(&x, &u, 4);
-  return x;
-}
-
-size_t ann_big_x_bytes(int k, int n) {
-  return (size_t)3 * ((k + 31) / 32) * ((n + 127) / 128 * 128) * 32 * 2;
-}
-
-void ann_big_pack_x(const float *W, int k, int n, void *dst) {
-  const int KG = (k + 31) / 32, NP = (n + 127) / 128 * 128;  // (whole 128-feature blocks)
-  uint16_t *d = static_cast<uint16_t *>(dst);
-  const size_t plane = (size_t)KG * NP * 32;
-  for (int g = 0; g < KG; ++g)
-    for (int c = 0; c < NP; ++c)
-      for (int kk = 0; kk < 32; ++kk) {
-        const int kr = 32 * g + kk;
-        const float x = (kr < k && c < n) ? W[(size_t)kr * n + c] : 0.0f;
-        const uint16_t h = bf16_rne_h(x);
-        const float r1 = x - bf16_f32_h(h);
-        const uint16_t m = bf16_rne_h(r1);
-        const float r2 = r1 - bf16_f32_h(m);
-        const size_t at = ((size_t)g * NP + c) * 32 + kk;
-        d[at] = h;
-        d[plane + at] = m;
-        d[2 * plane + at] = bf16_rne_h(r2);
-      }
-}
-
 void launch_ann_big(const AnnBigModel &m, const RobotDev &r, const double *pts, int64_t n,
                     float *ang, double *fk_err, bool check_limits, DevStats *S, hipStream_t st,
                     float *act, int64_t chunk_rows, int xmode) {

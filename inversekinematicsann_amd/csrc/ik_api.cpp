@@ -7,6 +7,7 @@
 // can be captured in a hipGraph.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -695,55 +696,14 @@ int ik_ann_load(ik_ctx *c, int n_layers, const int32_t *dims, const int32_t *act
     if (dims[l] < 1 || dims[l] > kAnnBigMaxWidth)
       return fail(IK_E_BADARG, "ik_ann_load: layer widths must be 1.." +
                                    std::to_string(kAnnBigMaxWidth));
-  // past the fused kernel's caps: the layered path (fp32, activations through HBM)
-  bool big = n_layers > kAnnMaxLayers;
-  for (int l = 0; l <= n_layers; ++l) big = big || dims[l] > kAnnMaxWidth;
   for (int l = 0; l < n_layers; ++l)
     if (acts[l] < IK_ACT_LINEAR || acts[l] > IK_ACT_SIGMOID)
       return fail(IK_E_BADARG, "ik_ann_load: unsupported activation code");
   int rc = set_dev(c);
   if (rc) return rc;
-  // one device buffer: per layer packed weights, padded bias and -- for the
-  // hidden layers that can take the bf16x6 mode (not the input layer, not a
-  // single-column-tile output layer) -- the split bf16 planes
-  std::vector<size_t> woff(n_layers), boff(n_layers), xoff(n_layers, 0), hoff(n_layers, 0);
-  std::vector<int> hexp(n_layers, 0);
-  // models wider than 512 run the wide fp32 kernel only: no split operands; the
-  // layered path (big) has its own bf16x6 planes (ann_big_pack_x)
-  bool wide = big;
-  for (int l = 0; l <= n_layers; ++l) wide = wide || dims[l] > 512;
-  bool planes = true;  // (dropped below when only the fp32 operands fit the device)
-  auto splittable = [&](int l) {
-    return planes && (!wide || big) && l > 0 && (dims[l + 1] + 31) / 32 > 1;
-  };
-  // fp16x3 also needs a bounded layer input: the layer before is tanh or sigmoid
-  auto halvable = [&](int l) {
-    return !big && splittable(l) &&
-           (acts[l - 1] == IK_ACT_TANH || acts[l - 1] == IK_ACT_SIGMOID);
-  };
-  size_t total = 0;
-  auto layout = [&]() {
-    total = 0;
-    for (int l = 0; l < n_layers; ++l) {
-      woff[l] = total;
-      total += ann_packed_floats(dims[l], dims[l + 1]) * 4;
-      total = (total + 255) & ~(size_t)255;
-      boff[l] = total;
-      total += (size_t)((dims[l + 1] + 31) / 32 * 32) * 4;
-      total = (total + 255) & ~(size_t)255;
-      if (splittable(l)) {
-        xoff[l] = total;
-        total += big ? ann_big_x_bytes(dims[l], dims[l + 1]) : ann_x_bytes(dims[l], dims[l + 1]);
-        total = (total + 255) & ~(size_t)255;
-      }
-      if (halvable(l)) {
-        hoff[l] = total;
-        total += ann_h_bytes(dims[l], dims[l + 1]);
-        total = (total + 255) & ~(size_t)255;
-      }
-    }
-  };
-  layout();
+  // one device buffer, per layer a section of packed weights, padded bias and
+  // the split modes' operands where the layer can take them (AnnLayout)
+  AnnLayout L(n_layers, dims, acts, true);
   // (the widths and depth are capped above, so `total` stays far below 2^64: at
   // most 4096 layers of a 16384 x 16384 product, ~4.4 TB -- but that may not fit
   // the device, and the host staging must not be one buffer of that size)
@@ -757,96 +717,59 @@ int ik_ann_load(ik_ctx *c, int n_layers, const int32_t *dims, const int32_t *act
   // least one 128-row tile of the widest padded layer (ann_launch takes up to
   // IKHIP_ANN_ACT_MB and falls back to fewer rows when that much is not free;
   // ADVICE r05), less what a previous model's buffers already hold
-  size_t act_min = 0;
-  if (big) {
-    size_t ld = 8;
-    for (int l = 0; l < n_layers; ++l) {
-      const size_t np = (size_t)(dims[l + 1] + 31) / 32 * 32;
-      ld = np > ld ? np : ld;
-    }
-    act_min = 2 * 128 * ld * sizeof(float);
-    act_min = act_min > c->ann_act_bytes ? act_min - c->ann_act_bytes : 0;
-  }
-  if (total + act_min > dev_free) {  // without the split planes (the split modes then run fp32)?
-    planes = false;
-    layout();
-  }
-  if (total + act_min > dev_free)
-    return fail(IK_E_HIP, "ik_ann_load: the packed model needs " + std::to_string(total) +
+  const size_t act_min = L.act_min > c->ann_act_bytes ? L.act_min - c->ann_act_bytes : 0;
+  // without the split planes?  (a split mode then runs fp32: ik_ann_effective_mode says so)
+  if (L.total + act_min > dev_free) L = AnnLayout(n_layers, dims, acts, false);
+  if (L.total + act_min > dev_free)
+    return fail(IK_E_HIP, "ik_ann_load: the packed model needs " + std::to_string(L.total) +
                               " bytes of device memory (+ " + std::to_string(act_min) +
                               " for its activations), " + std::to_string(dev_free) +
                               " are free");
-  // (without the planes a split mode runs fp32: ik_ann_effective_mode says so)
-  IK_HIP(hipMalloc(&c->ann_buf, total));
+  IK_HIP(hipMalloc(&c->ann_buf, L.total));
   char *base = static_cast<char *>(c->ann_buf);
   // pack and upload one layer's section at a time: the host holds
   // at most the largest layer's packed bytes, and an allocation failure is an
   // error code, not an exception leaving the C ABI
+  std::vector<int> hexp(n_layers, 0);
   try {
     std::vector<char> host;
     for (int l = 0; l < n_layers; ++l) {
-      const size_t end = l + 1 < n_layers ? woff[l + 1] : total;
-      host.assign(end - woff[l], 0);
-      char *h = host.data();  // the section starts at woff[l] in the model buffer
-      ann_pack_layer(W[l], dims[l], dims[l + 1], reinterpret_cast<float *>(h));
-      std::memcpy(h + (boff[l] - woff[l]), b[l], (size_t)dims[l + 1] * 4);
-      if (splittable(l)) {
-        if (big) ann_big_pack_x(W[l], dims[l], dims[l + 1], h + (xoff[l] - woff[l]));
-        else ann_pack_layer_x(W[l], dims[l], dims[l + 1], h + (xoff[l] - woff[l]));
-      }
-      if (halvable(l)) {
-        hexp[l] = ann_h_scale_exp(W[l], dims[l], dims[l + 1]);
-        ann_pack_layer_h(W[l], dims[l], dims[l + 1], hexp[l], h + (hoff[l] - woff[l]));
-      }
-      IK_HIP(hipMemcpy(base + woff[l], host.data(), host.size(), hipMemcpyHostToDevice));
+      host.assign(L.section_bytes(l), 0);
+      hexp[l] = ann_pack_section(L, l, W[l], b[l], host.data());
+      IK_HIP(hipMemcpy(base + L.woff[l], host.data(), host.size(), hipMemcpyHostToDevice));
     }
   } catch (const std::bad_alloc &) {
     (void)hipFree(c->ann_buf);
     c->ann_buf = nullptr;
     return fail(IK_E_HIP, "ik_ann_load: out of host memory staging the packed weights");
   }
-  c->ann_big = big;
-  c->ann_bigm.layers.clear();
-  if (big) {
-    AnnBigModel &bm = c->ann_bigm;
-    for (int l = 0; l < n_layers; ++l)
-      bm.layers.push_back({(dims[l] + 7) / 8 * 8, (dims[l + 1] + 31) / 32 * 32, acts[l],
-                           reinterpret_cast<const float *>(base + woff[l]),
-                           reinterpret_cast<const float *>(base + boff[l]),
-                           splittable(l) ? reinterpret_cast<const uint16_t *>(base + xoff[l])
-                                         : nullptr});
-    for (int i = 0; i < 3; ++i) {
-      bm.xm[i] = x_mean[i];
-      bm.xs[i] = x_scale[i];
-    }
-    for (int i = 0; i < 4; ++i) {
-      bm.ym[i] = y_mean[i];
-      bm.ys[i] = y_scale[i];
-    }
-    std::memset(&c->ann, 0, sizeof(c->ann));
-    c->ann_loaded = true;
-    return IK_OK;
-  }
+  c->ann_big = L.big;
+  AnnBigModel &bm = c->ann_bigm;
   AnnModelDev &m = c->ann;
+  bm.layers.clear();
   std::memset(&m, 0, sizeof(m));
-  m.n_layers = n_layers;
+  m.n_layers = L.big ? 0 : n_layers;
+  std::copy(x_mean, x_mean + 3, L.big ? bm.xm : m.xm);
+  std::copy(x_scale, x_scale + 3, L.big ? bm.xs : m.xs);
+  std::copy(y_mean, y_mean + 4, L.big ? bm.ym : m.ym);
+  std::copy(y_scale, y_scale + 4, L.big ? bm.ys : m.ys);
   for (int l = 0; l < n_layers; ++l) {
-    m.kp[l] = (dims[l] + 7) / 8 * 8;
-    m.np[l] = (dims[l + 1] + 31) / 32 * 32;
+    const float *wp = reinterpret_cast<const float *>(base + L.woff[l]);
+    const float *bias = reinterpret_cast<const float *>(base + L.boff[l]);
+    const char *wx = L.splittable[l] ? base + L.xoff[l] : nullptr;
+    if (L.big) {
+      bm.layers.push_back({L.kp(l), L.np(l), acts[l], wp, bias,
+                           reinterpret_cast<const uint16_t *>(wx)});
+      continue;
+    }
+    m.kp[l] = L.kp(l);
+    m.np[l] = L.np(l);
     m.act[l] = acts[l];
-    m.wp[l] = reinterpret_cast<const float4 *>(base + woff[l]);
-    m.bias[l] = reinterpret_cast<const float *>(base + boff[l]);
-    c->ann_wx[l] = splittable(l) ? base + xoff[l] : nullptr;
-    c->ann_wh[l] = halvable(l) ? base + hoff[l] : nullptr;
+    m.wp[l] = reinterpret_cast<const float4 *>(wp);
+    m.bias[l] = bias;
+    c->ann_wx[l] = wx;
+    c->ann_wh[l] = L.halvable[l] ? base + L.hoff[l] : nullptr;
     c->ann_hinv[l] = std::ldexp(1.0f, -hexp[l]);
-  }
-  for (int i = 0; i < 3; ++i) {
-    m.xm[i] = x_mean[i];
-    m.xs[i] = x_scale[i];
-  }
-  for (int i = 0; i < 4; ++i) {
-    m.ym[i] = y_mean[i];
-    m.ys[i] = y_scale[i];
   }
   c->ann_loaded = true;
   return IK_OK;

@@ -12,10 +12,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <cmath>
 #include <vector>
 
 #include "../../include/ikhip.h"
+#include "ik_ann_pack.h"
 
 namespace ikhip {
 
@@ -517,6 +519,23 @@ namespace ikhip {
       hipLaunchKernelGGL(K, G, B, SH, ST, __VA_ARGS__);                             \
   } while (0)
 
+// CUs of the current device, cached per device index (relaxed atomics: every
+// writer stores the same value)
+inline int num_cus() {
+  static std::atomic<int> cache[64];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::atomic<int> *slot = (dev >= 0 && dev < 64) ? &cache[dev] : nullptr;
+  int v = slot ? slot->load(std::memory_order_relaxed) : 0;
+  if (v <= 0) {
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        v <= 0)
+      v = 256;
+    if (slot) slot->store(v, std::memory_order_relaxed);
+  }
+  return v;
+}
+
 void launch_reset_stats(DevStats *S, hipStream_t st);
 void launch_check_limits(const RobotDev &r, const double *pts, int64_t n, DevStats *S,
                          hipStream_t st);
@@ -572,27 +591,19 @@ void launch_refine_f32(const RobotConstDev *rc, const double *pts, const float *
                        double tol, int max_iter, double damping, double *ang, int32_t *iters,
                        double *fk_err, bool check_limits, DevStats *S, hipStream_t st);
 
-constexpr int kAnnMaxLayers = 24;
-constexpr int kAnnMaxWidth = 1024;  // > 512: the wide build (ik_ann_w.hip), fp32 only
+// (the caps kAnnMaxLayers / kAnnMaxWidth and the weight packing: ik_ann_pack.h)
 struct AnnModelDev {
   int n_layers;
   int kp[kAnnMaxLayers];  // padded in-dim (multiple of 8)
   int np[kAnnMaxLayers];  // padded out-dim (multiple of 32)
   int act[kAnnMaxLayers];
-  const float4 *wp[kAnnMaxLayers];  // packed weights (see ik_ann.hip)
+  const float4 *wp[kAnnMaxLayers];  // packed weights (ann_pack_layer)
   const void *wx[kAnnMaxLayers];    // split modes: the layer's weight operand, else null
   float xinv[kAnnMaxLayers];        // fp16x3: 2^-k, k the layer's weight pre-scale exponent
   int xmode;                        // 0 fp32, 1 bf16x6, 2 fp16x3 (IK_ANN_*)
   const float *bias[kAnnMaxLayers];
   double xm[3], xs[3], ym[4], ys[4];
 };
-size_t ann_packed_floats(int k, int n);  // floats of one packed layer
-void ann_pack_layer(const float *W, int k, int n, float *dst);  // host-side packing
-size_t ann_x_bytes(int k, int n);  // bytes of one layer's bf16x6 weight operand
-void ann_pack_layer_x(const float *W, int k, int n, void *dst);
-size_t ann_h_bytes(int k, int n);  // bytes of one layer's fp16x3 weight operand
-int ann_h_scale_exp(const float *W, int k, int n);  // the weight pre-scale exponent k
-void ann_pack_layer_h(const float *W, int k, int n, int scale_exp, void *dst);
 size_t ann_debug_words();  // u64 slots of the diagnostic stamp buffer
 void launch_ann(const AnnModelDev &m, const RobotDev &r, const double *pts, int64_t n,
                 float *ang, double *fk_err, bool check_limits, DevStats *S, hipStream_t st,
@@ -603,9 +614,8 @@ void launch_ann_wide(const AnnModelDev &m, const RobotDev &r, const double *pts,
 
 // Models outside the fused kernel's caps (more than kAnnMaxLayers layers or a
 // layer wider than kAnnMaxWidth): layer at a time through HBM (ik_ann_big.hip),
-// fp32, or bf16x6 for the hidden layers after the first in a split mode.  Bounds:
-constexpr int kAnnBigMaxLayers = 4096;
-constexpr int kAnnBigMaxWidth = 16384;
+// fp32, or bf16x6 for the hidden layers after the first in a split mode, up to
+// kAnnBigMaxLayers layers of kAnnBigMaxWidth.
 struct AnnBigLayer {
   int kp, np, act;   // padded in-dim (multiple of 8), padded out-dim (multiple of 32)
   const float *wp;   // packed weights (ann_pack_layer order)
@@ -618,10 +628,6 @@ struct AnnBigModel {
 };
 // floats per activation row (the widest padded layer, at least 8)
 size_t ann_big_ld(const AnnBigModel &m);
-// the layered path's bf16x6 weight planes: [plane][ceil(k / 32)][n rounded up to
-// 128][32] bf16, ann_big_x_bytes(k, n) bytes
-size_t ann_big_x_bytes(int k, int n);
-void ann_big_pack_x(const float *W, int k, int n, void *dst);
 // rows per chunk that fit two activation buffers in act_bytes (multiple of 128)
 int64_t ann_big_rows(const AnnBigModel &m, size_t act_bytes);
 // act: 2 * chunk_rows * ann_big_ld(m) floats

@@ -16,7 +16,6 @@
 //    joints never touch HBM.
 //  * simple: everything in one kernel, one point per lane, no refill.
 // Per point the state is 4 joints + goal (15 doubles) held in VGPRs.
-#include <atomic>
 #include <cmath>
 
 #include "ik_common.h"
@@ -1335,23 +1334,6 @@ static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 size_t fabrik_scratch_bytes(int64_t n) {
   // work order: perm n int32, cell n uint16
   return up256((size_t)n * 4) + up256((size_t)n * 2) + 1024;
-}
-
-// CUs of the current device, cached per device index (relaxed atomics: every
-// writer stores the same value)
-static int num_cus() {
-  static std::atomic<int> cache[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::atomic<int> *slot = (dev >= 0 && dev < 64) ? &cache[dev] : nullptr;
-  int v = slot ? slot->load(std::memory_order_relaxed) : 0;
-  if (v <= 0) {
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        v <= 0)
-      v = 256;
-    if (slot) slot->store(v, std::memory_order_relaxed);
-  }
-  return v;
 }
 
 template <int REFILL_MIN, bool ORD>

@@ -257,15 +257,6 @@ void launch_fk_n(int nj, const double *dh, const double *ang, int64_t n, double 
   kt_end(st);
 }
 
-static int fk_cus() {
-  int dev = 0, cus = 0;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      cus <= 0)
-    cus = 256;
-  return cus;
-}
-
 void launch_fk(const RobotDev &r, const double *ang, int64_t n, double *xyz, double *joints,
                DevStats *S, hipStream_t st) {
   if (n <= 0) return;
@@ -283,7 +274,7 @@ void launch_fk(const RobotDev &r, const double *ang, int64_t n, double *xyz, dou
     // resident blocks only (8 per CU): every lane walks several points
     // (2, 4, 6, 8 blocks per CU or one point per lane all measured 17.0-17.3 us per
     // 1M points: at that size the launch's fixed cost, ~6 us, is a third of it)
-    const unsigned cap = (unsigned)fk_cus() * 8;
+    const unsigned cap = (unsigned)num_cus() * 8;
     const unsigned grid = grid_all < cap ? grid_all : cap;
     IK_LAUNCH(fk_kernel, dim3(grid), dim3(256), 0, st, r, kc, ang, n, xyz, S);
   }

@@ -10,9 +10,9 @@ import re
 from tests.conftest import ROOT
 
 CSRC = os.path.join(ROOT, "inversekinematicsann_amd", "csrc")
-# build-wide switches that are not tuning knobs: the diagnostic build and the two
-# translation units that re-include ik_ann.hip
-NOT_KNOBS = {"IKHIP_DIAG", "IKHIP_ANN_WIDE", "IKHIP_ANN_X_TU", "IKHIP_PHASE_MARKS"}
+# build-wide switches that are not tuning knobs: the diagnostic build and the wide
+# build of ik_ann_kernel.h (ik_ann_w.hip)
+NOT_KNOBS = {"IKHIP_DIAG", "IKHIP_ANN_WIDE", "IKHIP_PHASE_MARKS"}
 DELETED = {"IKHIP_EXP_L1W", "IKHIP_FAB_FUSED_SCATTER", "IKHIP_FAB_PREP_CARRY", "IKHIP_ANN_CLAIM",
            "IKHIP_ANN_H16", "IKHIP_ANN_X16", "IKHIP_ANN_DYN", "IKHIP_ANN_HSWZ",
            "IKHIP_ANN_BIAS_FIRST", "IKHIP_ANN_H16_PATTERN", "IKHIP_ANN_X16_PATTERN",

@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256) void mfma_bench(int iters, float *out, unsigne
   }
 }
 
-// The fp16x3 layer's K loop alone (ik_ann.hip layer_gemm_h16 / step_h16,
+// The fp16x3 layer's K loop alone (ik_ann_kernel.h layer_gemm_h16 / step_h16,
 // restated: 4 waves per CU, MR = 2 x NR = 4 tiles of 16x16x32 sub-tiles, the weight
 // stream through a buffer descriptor from a 1 MiB L2-resident operand, a 2-step
 // ring, the activations from LDS split planes, pattern 2), LAYERS x 16 steps with
@@ -308,7 +308,7 @@ struct KSplit2 {
 struct KW {
   h8 p[4][2][2];  // [tile][feature half][plane]
 };
-constexpr int kKLd = 516;  // floats per LDS row (ik_ann.hip kLd)
+constexpr int kKLd = 516;  // floats per LDS row (ik_ann_kernel.h kLd)
 // V 4: as V 0, but layer l reads weight slice l % 12 of a 12 MiB operand (the
 // reference model's 11 hidden layers do not fit one XCD's 4 MB L2); V 5: each
 // workgroup starts at its own slice (blockIdx % 12), as drifted workgroups are.
