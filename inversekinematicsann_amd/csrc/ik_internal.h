@@ -1,6 +1,7 @@
 // ik_internal.h -- the context behind the C ABI and the helpers its
 // translation units share (ik_api.cpp: single-device calls; ik_pipe.cpp: the
-// chunked host-pointer pipeline; ik_shard.hip: the RCCL-sharded calls).  Not
+// chunked host-pointer pipeline; ik_shard.hip: the RCCL-sharded calls, whose
+// plan / tail / histogram arithmetic is the host-only ik_shard_plan.cpp).  Not
 // installed; include/ikhip.h is the interface.
 #pragma once
 

@@ -20,6 +20,8 @@
 // histogram (quantiles) travel in a per-rank tail block with the last chunk,
 // beside first_oob / first_err (lowest GLOBAL index: the reference's sequential
 // exception precedence), the iteration sum and the capped count.  No all_reduce.
+// The arithmetic every rank must agree on (plan, tail reduction, histogram edges
+// and quantiles) is ik_shard_plan.cpp, host only.
 //
 // RCCL is loaded at run time (dlopen): a librccl the process already holds
 // (torch ships one, built against the HIP runtime the process uses; found by
@@ -30,7 +32,6 @@
 
 #include <chrono>
 #include <climits>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,6 +40,7 @@
 #include <thread>
 
 #include "ik_internal.h"
+#include "ik_shard_plan.h"
 
 using namespace ikhip;
 using namespace ikapi;
@@ -249,30 +251,6 @@ bool comm_drained(const IkComm &m) {
   return true;
 }
 
-bool plan_args_ok(int64_t n, int nranks, int chunks) {
-  return n >= 0 && n < ((int64_t)1 << 48) && nranks >= 1 && nranks <= 1024 && chunks >= 1 &&
-         chunks <= IK_MAX_GATHER_CHUNKS;
-}
-
-// S = ceil(n / (C g)); the chunks that hold rows; the rows of the full ones.
-void make_plan(int64_t n, int g, int C, ik_shard_plan *p) {
-  std::memset(p, 0, sizeof(*p));
-  p->n = n;
-  p->nranks = g;
-  const int64_t cg = (int64_t)C * g;
-  p->part_rows = n > 0 ? (n + cg - 1) / cg : 0;
-  const int64_t per_chunk = p->part_rows * g;
-  p->chunks = n > 0 ? (int)((n + per_chunk - 1) / per_chunk) : 0;
-  p->full_rows = per_chunk > 0 ? (n / per_chunk) * per_chunk : 0;
-}
-
-void part_of(const ik_shard_plan &p, int r, int c, int64_t *b, int64_t *e) {
-  const int64_t S = p.part_rows;
-  const int64_t lo = ((int64_t)c * p.nranks + r) * S, hi = lo + S;
-  *b = lo < p.n ? lo : p.n;
-  *e = hi < p.n ? hi : p.n;
-}
-
 }  // namespace
 
 namespace ikhip {
@@ -384,8 +362,7 @@ int env_chunks() {
   return env;
 }
 
-int auto_chunks(ik_ctx *c, int method, int64_t n) {
-  const IkComm &m = c->comm;
+int auto_chunks(const IkComm &m) {
   int C = m.chunks_req;
   if (C <= 0) C = env_chunks();
   // automatic: one chunk for both methods.  ANN's gather is ~0.5 % of the solve;
@@ -399,8 +376,6 @@ int auto_chunks(ik_ctx *c, int method, int64_t n) {
   // every rank makes the same one (ik_comm_init checks the environment's, every
   // call's tail its plan); bench.py's gather check compares the gathered rows
   // with a plain re-solve bit for bit on every N > 1 run.
-  (void)n;
-  (void)method;
   if (C <= 0) C = 1;
   return C > IK_MAX_GATHER_CHUNKS ? IK_MAX_GATHER_CHUNKS : C;
 }
@@ -515,6 +490,30 @@ int sharded_enqueue(ik_ctx *c, int method, const ik_shard_plan &P, Region *R, in
     return res ? rccl_fail(r, start ? "ncclGroupStart" : "ncclGroupEnd", res) : IK_OK;
   };
   const int64_t S = P.part_rows;
+  // Chunk k's exchange: the comm stream waits for the solve stream's work so
+  // far, then one group of all-gathers between the events that time it -- the
+  // chunk's g S rows of each of the first nr regions (in place from row cb, or
+  // in the stage) and, with the last chunk, every rank's tail block.  nr = 0 is
+  // the empty batch's tail-only exchange, which ik_kernel_times does not list.
+  auto exchange = [&](int k, int64_t cb, bool staged, int nr, bool last) -> int {
+    IK_HIP(hipEventRecord(m.ev_solved[k], c->stream));
+    IK_HIP(hipStreamWaitEvent(m.cs, m.ev_solved[k], 0));
+    if (nr) kt_span_begin("rccl_all_gather", m.cs);
+    IK_HIP(hipEventRecord(m.ev_gs[k], m.cs));
+    int er = group(true);
+    if (er) return er;
+    for (int q = 0; q < nr && !er; ++q) {
+      char *base = staged ? R[q].stage : R[q].out + cb * R[q].rb;
+      const size_t cnt = (size_t)S * R[q].rb;
+      er = gather(base + (size_t)me * cnt, base, cnt, false);
+    }
+    if (last && !er) er = gather(m.tail_send, m.tail_recv, sizeof(IkTailBlock), true);
+    const int end = group(false);  // a failed gather's group is ended too, its error kept
+    if (er || (er = end)) return er;
+    IK_HIP(hipEventRecord(m.ev_ge[k], m.cs));
+    if (nr) kt_end(m.cs);
+    return IK_OK;
+  };
   m.last_chunks = C;
   m.last_hist = fk_err_dev != nullptr;
   // the tail block: zeroed (histogram) before any part adds to it
@@ -560,25 +559,7 @@ int sharded_enqueue(ik_ctx *c, int method, const ik_shard_plan &P, Region *R, in
       IK_LAUNCH(pack_tail_kernel, dim3(1), dim3(64), 0, c->stream, ta, m.tail_send);
     }
     IK_HIP(hipGetLastError());
-    IK_HIP(hipEventRecord(m.ev_solved[k], c->stream));
-    IK_HIP(hipStreamWaitEvent(m.cs, m.ev_solved[k], 0));
-    // chunk k's rows of every rank, in place (+ every rank's tail block with the last)
-    kt_span_begin("rccl_all_gather", m.cs);
-    IK_HIP(hipEventRecord(m.ev_gs[k], m.cs));
-    if ((rc = group(true))) return rc;
-    for (int q = 0; q < nreg && !rc; ++q) {
-      char *base = staged ? R[q].stage : R[q].out + cb * R[q].rb;
-      const size_t cnt = (size_t)S * R[q].rb;
-      rc = gather(base + (size_t)me * cnt, base, cnt, false);
-    }
-    if (last && !rc) rc = gather(m.tail_send, m.tail_recv, sizeof(IkTailBlock), true);
-    if (rc) {
-      (void)group(false);
-      return rc;
-    }
-    if ((rc = group(false))) return rc;
-    IK_HIP(hipEventRecord(m.ev_ge[k], m.cs));
-    kt_end(m.cs);
+    if ((rc = exchange(k, cb, staged, nreg, last))) return rc;
     if (staged && cb < P.n)  // the ragged chunk: its rows are in global order in the stage
       for (int q = 0; q < nreg; ++q)
         IK_HIP(hipMemcpyAsync(R[q].out + cb * R[q].rb, R[q].stage, (size_t)(P.n - cb) * R[q].rb,
@@ -589,17 +570,7 @@ int sharded_enqueue(ik_ctx *c, int method, const ik_shard_plan &P, Region *R, in
     ta.K = 1;
     IK_LAUNCH(pack_tail_kernel, dim3(1), dim3(64), 0, c->stream, ta, m.tail_send);
     IK_HIP(hipGetLastError());
-    IK_HIP(hipEventRecord(m.ev_solved[0], c->stream));
-    IK_HIP(hipStreamWaitEvent(m.cs, m.ev_solved[0], 0));
-    IK_HIP(hipEventRecord(m.ev_gs[0], m.cs));
-    if ((rc = group(true))) return rc;
-    rc = gather(m.tail_send, m.tail_recv, sizeof(IkTailBlock), true);
-    if (rc) {
-      (void)group(false);
-      return rc;
-    }
-    if ((rc = group(false))) return rc;
-    IK_HIP(hipEventRecord(m.ev_ge[0], m.cs));
+    if ((rc = exchange(0, 0, false, 0, true))) return rc;
     m.last_chunks = 1;
   }
   // the call ends on the solve stream: it waits for the gathers, then the tails
@@ -623,9 +594,7 @@ int sharded_enqueue(ik_ctx *c, int method, const ik_shard_plan &P, Region *R, in
 template <class Solve>
 int sharded_run(ik_ctx *c, int method, const ik_shard_plan &P, Region *R, int nreg,
                 double *fk_err_dev, Solve solve) {
-  IkComm &m = c->comm;
-  if (m.broken) return fail(IK_E_RCCL, "communicator aborted earlier (" + m.why +
-                                           "); ik_comm_destroy and ik_comm_init again");
+  IkComm &m = c->comm;  // (not aborted: sharded_call has refused that)
   int gathers = 0;
   const int rc = sharded_enqueue(c, method, P, R, nreg, fk_err_dev, solve, &gathers);
   if (rc == IK_OK) return IK_OK;
@@ -699,8 +668,7 @@ int sharded_stats(ik_ctx *c, ik_stats *stats) {
   if (!stats) return IK_OK;
   ik_shard_tail t[1024];
   for (int r = 0; r < m.nranks; ++r) t[r] = m.h_tails[r].t;
-  rc = ik_tail_reduce(t, m.nranks, stats);
-  if (rc) return rc;
+  tail_reduce(t, m.nranks, stats);
   float tot = 0.0f;
   for (int k = 0; k < m.last_chunks; ++k) {
     float ms = 0.0f;
@@ -712,17 +680,21 @@ int sharded_stats(ik_ctx *c, ik_stats *stats) {
 
 bool comm_release(ik_ctx *c) {
   IkComm &m = c->comm;
-  // a live communicator's last call first ends, or is aborted at the deadline
-  if (m.comm && !m.broken && m.ev_end_set) (void)comm_wait(c, m.ev_end, "the last sharded call");
-  if (m.broken && !comm_drained(m)) {
-    // aborted work still queued: freeing its buffers would block on it, so
-    // they are left to the process's end (the communicator is unusable anyway)
+  // a fresh IkComm that keeps the caller's settings (chunks, deadline)
+  auto reset = [&] {
     const int keep_chunks = m.chunks_req;
     const double keep_t = m.timeout_s;
     m = IkComm();
     m.chunks_req = keep_chunks;
     m.timeout_s = keep_t;
     c->last_sharded = false;
+  };
+  // a live communicator's last call first ends, or is aborted at the deadline
+  if (m.comm && !m.broken && m.ev_end_set) (void)comm_wait(c, m.ev_end, "the last sharded call");
+  if (m.broken && !comm_drained(m)) {
+    // aborted work still queued: freeing its buffers would block on it, so
+    // they are left to the process's end (the communicator is unusable anyway)
+    reset();
     return false;
   }
   if (m.cs) (void)hipStreamSynchronize(m.cs);
@@ -744,12 +716,7 @@ bool comm_release(ik_ctx *c) {
   if (m.ev_done) (void)hipEventDestroy(m.ev_done);
   if (m.ev_end) (void)hipEventDestroy(m.ev_end);
   if (m.cs) (void)hipStreamDestroy(m.cs);
-  const int keep_chunks = m.chunks_req;
-  const double keep_t = m.timeout_s;
-  m = IkComm();
-  m.chunks_req = keep_chunks;
-  m.timeout_s = keep_t;
-  c->last_sharded = false;
+  reset();
   return true;
 }
 
@@ -956,36 +923,15 @@ int ik_shard_range(int64_t n, int nranks, int rank, int64_t *begin, int64_t *end
   return IK_OK;
 }
 
-// Rank order, as one process would meet the points: the lowest global failing
-// index wins, sums add up, FK-error max over ranks.
 int ik_tail_reduce(const ik_shard_tail *t, int nranks, ik_stats *s) {
   if (!t || !s || nranks < 1) return fail(IK_E_BADARG, "ik_tail_reduce: bad args");
-  std::memset(s, 0, sizeof(*s));
-  s->first_oob = -1;
-  s->first_err = -1;
-  s->first_err_code = IK_OK;
-  for (int r = 0; r < nranks; ++r) {
-    if (t[r].first_oob >= 0 && (s->first_oob < 0 || t[r].first_oob < s->first_oob))
-      s->first_oob = t[r].first_oob;
-    if (t[r].first_err >= 0 && (s->first_err < 0 || t[r].first_err < s->first_err)) {
-      s->first_err = t[r].first_err;
-      s->first_err_code = t[r].first_err_code;
-    }
-    s->max_iters = t[r].max_iters > s->max_iters ? t[r].max_iters : s->max_iters;
-    s->sum_iters += t[r].sum_iters;
-    s->n_capped += t[r].n_capped;
-    s->max_fk_err = t[r].max_fk_err > s->max_fk_err ? t[r].max_fk_err : s->max_fk_err;
-    s->sum_fk_err += t[r].sum_fk_err;
-  }
+  tail_reduce(t, nranks, s);
   return IK_OK;
 }
 
 int ik_fkhist_bin(double e) { return fkhist_bin(e); }
 
-double ik_fkhist_upper(int bin) {
-  if (bin < 0 || bin >= IK_FKHIST_BINS - 1) return bin < 0 ? 0.0 : HUGE_VAL;
-  return std::ldexp(1.0 + (double)(bin % 16 + 1) / 16.0, bin / 16 - 64);
-}
+double ik_fkhist_upper(int bin) { return fkhist_upper(bin); }
 
 int ik_fk_err_quantile(ik_ctx *c, double q, double *out) {
   if (!c || !out || !(q > 0.0 && q <= 1.0)) return fail(IK_E_BADARG, "ik_fk_err_quantile: bad args");
@@ -995,193 +941,151 @@ int ik_fk_err_quantile(ik_ctx *c, double q, double *out) {
   if (rc) return rc;
   if ((rc = comm_wait(c, c->comm.ev_end, "the last sharded call"))) return rc;
   const IkComm &m = c->comm;
-  uint64_t tot = 0;
-  for (int r = 0; r < m.nranks; ++r)
-    for (int b = 0; b < IK_FKHIST_BINS; ++b) tot += m.h_tails[r].hist[b];
-  *out = NAN;
-  if (tot == 0) return IK_OK;
-  const uint64_t want = (uint64_t)std::ceil(q * (double)tot);
-  uint64_t cum = 0;
-  for (int b = 0; b < IK_FKHIST_BINS; ++b) {
-    for (int r = 0; r < m.nranks; ++r) cum += m.h_tails[r].hist[b];
-    if (cum >= (want ? want : 1)) {
-      *out = ik_fkhist_upper(b);
-      break;
-    }
-  }
+  const uint32_t *hists[1024];
+  for (int r = 0; r < m.nranks; ++r) hists[r] = m.h_tails[r].hist;
+  *out = fkhist_quantile(hists, m.nranks, q);
   return IK_OK;
 }
 
-static int sharded_common(ik_ctx *c, int flags, const char *who) {
-  if (!c) return fail(IK_E_BADARG, std::string(who) + ": NULL context");
-  if (!c->comm.comm) return fail(IK_E_BADARG, std::string(who) + ": no communicator (ik_comm_init)");
-  // (the callers check their arrays next, then `ang` with check_flags again)
-  const int rc = check_flags(who, flags);
-  return rc ? rc : set_dev(c);
-}
+}  // extern "C"
 
-// Host pointers: device scratch holds the points (the rank's parts, at their
-// global rows), the gathered outputs (n rows each) and the FK errors.
-struct HostStage {
-  char *pts, *out[2], *fk;
+namespace {
+
+// One sharded call as its entry point describes it.
+struct ShardCall {
+  const char *who;  // the entry point's name
+  int method;
+  const double *pts;
+  int64_t n;
+  int flags;
+  ik_stats *stats;
+  int nreg, rb[2];  // the gathered outputs (1 or 2): their row bytes ...
+  void *out[2];     // ... and the caller's arrays
+  double *fk_err;   // nullable; only this rank's rows are written
+  size_t (*work_bytes)(int64_t);  // device work area of a part of that many rows (null: none)
 };
 
-static int host_stage(ik_ctx *c, int64_t n, const int *rb, int nreg, bool fk, size_t extra,
-                      HostStage *h, char **extra_at) {
-  Stage::Carve cv;
-  const size_t o_extra = cv.add(extra), o_pts = cv.add((size_t)n * 24);
-  size_t o_out[2] = {0, 0};
-  for (int q = 0; q < nreg; ++q) o_out[q] = cv.add((size_t)n * rb[q]);
-  const size_t o_fk = fk ? cv.add((size_t)n * 8) : 0;
-  int rc = ensure_scratch(c, cv.total);
+// The refusals both entry points share, in their order: no context, no
+// communicator, the flags, the arrays and the entry point's own arguments
+// (args_ok), a misaligned device `ang`.
+int sharded_refusals(ik_ctx *c, const char *who, int flags, const double *pts, int64_t n,
+                     const void *ang, bool args_ok) {
+  if (!c) return fail(IK_E_BADARG, std::string(who) + ": NULL context");
+  if (!c->comm.comm) return fail(IK_E_BADARG, std::string(who) + ": no communicator (ik_comm_init)");
+  int rc = check_flags(who, flags);
+  if (rc || (rc = set_dev(c))) return rc;
+  if (n < 0 || n >= ((int64_t)1 << 48) || (n > 0 && (!pts || !ang)) || !args_ok)
+    return fail(IK_E_BADARG, std::string(who) + ": bad args");
+  return check_flags(who, flags, ang);
+}
+
+// A sharded call once its arguments passed: the plan, the communicator's
+// buffers, the host staging, the chunks' solves and gathers, the copies back,
+// the stats.  launch(j, pts, work) enqueues the solve of part j, whose first
+// point is at pts (device), with the call's work area.  Host pointers: device
+// scratch holds the work area, the points (the rank's parts, at their global
+// rows), the gathered outputs (n rows each) and the FK errors.
+template <class Launch>
+int sharded_call(ik_ctx *c, const ShardCall &s, Launch launch) {
+  IkComm &m = c->comm;
+  KtScope kts(c);
+  if (m.broken)
+    return fail(IK_E_RCCL, std::string(s.who) + ": communicator aborted earlier (" + m.why + ")");
+  m.last_req = auto_chunks(m);
+  ik_shard_plan P;
+  make_plan(s.n, m.nranks, m.last_req, &P);
+  // the stage: the ragged chunk's g S rows of every region
+  Stage::Carve sv;
+  size_t o_stage[2] = {0, 0};
+  for (int q = 0; q < s.nreg; ++q) o_stage[q] = sv.add((size_t)P.part_rows * m.nranks * s.rb[q]);
+  int rc = ensure_comm_state(c, sv.total);
   if (rc) return rc;
-  char *s = static_cast<char *>(c->scratch);
-  *extra_at = s + o_extra;
-  h->pts = s + o_pts;
-  for (int q = 0; q < 2; ++q) h->out[q] = q < nreg ? s + o_out[q] : nullptr;
-  h->fk = fk ? s + o_fk : nullptr;
-  return IK_OK;
-}
-
-// The rank's parts of the points, host -> scratch at their global rows.
-static int host_points_in(ik_ctx *c, const ik_shard_plan &P, const double *pts, char *dst) {
-  for (int k = 0; k < P.chunks; ++k) {
-    int64_t b, e;
-    part_of(P, c->comm.rank, k, &b, &e);
-    if (e > b)
-      IK_HIP(hipMemcpyAsync(dst + b * 24, pts + 3 * b, (size_t)(e - b) * 24,
-                            hipMemcpyHostToDevice, c->stream));
-  }
-  return IK_OK;
-}
-
-// After the call: the gathered rows (all n) and this rank's FK errors to the host.
-static int host_results_out(ik_ctx *c, const ik_shard_plan &P, const Region *R, int nreg,
-                            char *const *host_out, const char *dfk, double *hfk) {
-  for (int q = 0; q < nreg; ++q)
-    if (host_out[q] && P.n > 0)
-      IK_HIP(hipMemcpyAsync(host_out[q], R[q].out, (size_t)P.n * R[q].rb, hipMemcpyDeviceToHost,
-                            c->stream));
-  if (hfk)
+  Region R[2] = {};
+  for (int q = 0; q < s.nreg; ++q)
+    R[q] = {s.rb[q], static_cast<char *>(s.out[q]), static_cast<char *>(m.stage) + o_stage[q]};
+  // this rank's parts of an n-row array, which both sides hold at their global rows
+  auto copy_own_rows = [&](void *dst, const void *src, int rb, hipMemcpyKind kind) -> int {
     for (int k = 0; k < P.chunks; ++k) {
       int64_t b, e;
-      part_of(P, c->comm.rank, k, &b, &e);
+      part_of(P, m.rank, k, &b, &e);
       if (e > b)
-        IK_HIP(hipMemcpyAsync(hfk + b, dfk + b * 8, (size_t)(e - b) * 8, hipMemcpyDeviceToHost,
+        IK_HIP(hipMemcpyAsync(static_cast<char *>(dst) + b * rb,
+                              static_cast<const char *>(src) + b * rb, (size_t)(e - b) * rb, kind,
                               c->stream));
     }
-  return IK_OK;
-}
-
-int ik_ann_solve_sharded(ik_ctx *c, const double *pts, int64_t n, float *ang, double *fk_err,
-                         int flags, ik_stats *stats) {
-  int rc = sharded_common(c, flags, "ik_ann_solve_sharded");
-  if (rc) return rc;
-  if (n < 0 || n >= ((int64_t)1 << 48) || (n > 0 && (!pts || !ang)))
-    return fail(IK_E_BADARG, "ik_ann_solve_sharded: bad args");
-  if ((rc = check_flags("ik_ann_solve_sharded", flags, ang))) return rc;
-  if (!c->ann_loaded) return fail(IK_E_NOMODEL, "ik_ann_solve_sharded: no model loaded");
-  KtScope kts(c);
-  const bool dev = flags & IK_F_DEVICE;
-  const int g = c->comm.nranks;
-  ik_shard_plan P;
-  if (c->comm.broken)
-    return fail(IK_E_RCCL, "ik_ann_solve_sharded: communicator aborted earlier (" +
-                               c->comm.why + ")");
-  c->comm.last_req = auto_chunks(c, IK_METHOD_ANN, n);
-  make_plan(n, g, c->comm.last_req, &P);
-  const size_t stage = Stage::up((size_t)P.part_rows * g * 16);
-  if ((rc = ensure_comm_state(c, stage))) return rc;
-  Region R[1] = {{16, reinterpret_cast<char *>(ang), static_cast<char *>(c->comm.stage)}};
-  const double *dp = pts;
-  double *dfk = fk_err;
-  HostStage hs;
+    return IK_OK;
+  };
+  const size_t b_work = s.work_bytes ? Stage::up(s.work_bytes(P.part_rows)) : 0;
+  const double *dp = s.pts;
+  double *dfk = s.fk_err;
+  char *work = nullptr;
+  const bool dev = s.flags & IK_F_DEVICE;
   if (!dev) {
     // pageable host copies wait for the stream: the previous call's end first
-    if (c->comm.ev_end_set && (rc = comm_wait(c, c->comm.ev_end, "the previous sharded call")))
-      return rc;
-    const int rb[1] = {16};
-    char *unused = nullptr;
-    if ((rc = host_stage(c, n, rb, 1, fk_err != nullptr, 0, &hs, &unused))) return rc;
-    if ((rc = host_points_in(c, P, pts, hs.pts))) return rc;
-    dp = reinterpret_cast<const double *>(hs.pts);
-    R[0].out = hs.out[0];
-    dfk = reinterpret_cast<double *>(hs.fk);
+    if (m.ev_end_set && (rc = comm_wait(c, m.ev_end, "the previous sharded call"))) return rc;
+    Stage::Carve cv;
+    const size_t o_work = cv.add(b_work), o_pts = cv.add((size_t)s.n * 24);
+    size_t o_out[2] = {0, 0};
+    for (int q = 0; q < s.nreg; ++q) o_out[q] = cv.add((size_t)s.n * s.rb[q]);
+    const size_t o_fk = s.fk_err ? cv.add((size_t)s.n * 8) : 0;
+    if ((rc = ensure_scratch(c, cv.total))) return rc;
+    char *at = static_cast<char *>(c->scratch);
+    work = at + o_work;
+    if ((rc = copy_own_rows(at + o_pts, s.pts, 24, hipMemcpyHostToDevice))) return rc;
+    dp = reinterpret_cast<const double *>(at + o_pts);
+    for (int q = 0; q < s.nreg; ++q) R[q].out = at + o_out[q];
+    dfk = s.fk_err ? reinterpret_cast<double *>(at + o_fk) : nullptr;
+  } else if (b_work) {
+    if ((rc = ensure_scratch(c, b_work))) return rc;
+    work = static_cast<char *>(c->scratch);
   }
-  const bool limits = !(flags & IK_F_NO_LIMITS);
-  rc = sharded_run(c, IK_METHOD_ANN, P, R, 1, dfk, [&](const PartJob &j) {
-    return ann_launch(c, dp + 3 * j.b, j.m, reinterpret_cast<float *>(j.at[0]), j.fk_err, limits,
-                      j.S);
-  });
+  rc = sharded_run(c, s.method, P, R, s.nreg, dfk,
+                   [&](const PartJob &j) { return launch(j, dp + 3 * j.b, work); });
   if (rc) return rc;
   if (!dev) {
     // copies into pageable host memory block the thread until the stream
-    // reaches them: first the bounded wait for the gathers
-    if ((rc = comm_wait(c, c->comm.ev_end, "the sharded call"))) return rc;
-    char *ho[1] = {reinterpret_cast<char *>(ang)};
-    if ((rc = host_results_out(c, P, R, 1, ho, hs.fk, fk_err))) return rc;
+    // reaches them: first the bounded wait for the gathers; then the gathered
+    // rows (all n) and this rank's FK errors
+    if ((rc = comm_wait(c, m.ev_end, "the sharded call"))) return rc;
+    for (int q = 0; q < s.nreg && P.n > 0; ++q)
+      IK_HIP(hipMemcpyAsync(s.out[q], R[q].out, (size_t)P.n * s.rb[q], hipMemcpyDeviceToHost,
+                            c->stream));
+    if (s.fk_err && (rc = copy_own_rows(s.fk_err, dfk, 8, hipMemcpyDeviceToHost))) return rc;
   }
-  if (flags & IK_F_ASYNC) return IK_OK;
-  return sharded_stats(c, stats);
+  if (s.flags & IK_F_ASYNC) return IK_OK;
+  return sharded_stats(c, s.stats);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ik_ann_solve_sharded(ik_ctx *c, const double *pts, int64_t n, float *ang, double *fk_err,
+                         int flags, ik_stats *stats) {
+  const char *who = "ik_ann_solve_sharded";
+  if (const int rc = sharded_refusals(c, who, flags, pts, n, ang, true)) return rc;
+  if (!c->ann_loaded) return fail(IK_E_NOMODEL, std::string(who) + ": no model loaded");
+  const ShardCall s = {who, IK_METHOD_ANN, pts, n, flags, stats, 1, {16, 0}, {ang, nullptr},
+                       fk_err, nullptr};
+  const bool limits = !(flags & IK_F_NO_LIMITS);
+  return sharded_call(c, s, [&](const PartJob &j, const double *p, void *) {
+    return ann_launch(c, p, j.m, reinterpret_cast<float *>(j.at[0]), j.fk_err, limits, j.S);
+  });
 }
 
 int ik_fabrik_solve_sharded(ik_ctx *c, const double *pts, int64_t n, double tol,
                             int32_t max_iter, double *ang, int32_t *iters, double *fk_err,
                             int flags, ik_stats *stats) {
-  int rc = sharded_common(c, flags, "ik_fabrik_solve_sharded");
-  if (rc) return rc;
-  if (n < 0 || n >= ((int64_t)1 << 48) || (n > 0 && (!pts || !ang)) || max_iter < 0)
-    return fail(IK_E_BADARG, "ik_fabrik_solve_sharded: bad args");
-  if ((rc = check_flags("ik_fabrik_solve_sharded", flags, ang))) return rc;
-  KtScope kts(c);
-  const bool dev = flags & IK_F_DEVICE;
-  const int g = c->comm.nranks;
-  ik_shard_plan P;
-  if (c->comm.broken)
-    return fail(IK_E_RCCL, "ik_fabrik_solve_sharded: communicator aborted earlier (" +
-                               c->comm.why + ")");
-  c->comm.last_req = auto_chunks(c, IK_METHOD_FABRIK, n);
-  make_plan(n, g, c->comm.last_req, &P);
-  const int nreg = iters ? 2 : 1;
-  const size_t b_ang_st = Stage::up((size_t)P.part_rows * g * 32);
-  const size_t stage = b_ang_st + (iters ? Stage::up((size_t)P.part_rows * g * 4) : 0);
-  if ((rc = ensure_comm_state(c, stage))) return rc;
-  char *st = static_cast<char *>(c->comm.stage);
-  Region R[2] = {{32, reinterpret_cast<char *>(ang), st},
-                 {4, reinterpret_cast<char *>(iters), st + b_ang_st}};
-  const size_t b_work = Stage::up(fabrik_scratch_bytes(P.part_rows));
-  const double *dp = pts;
-  double *dfk = fk_err;
-  char *work = nullptr;
-  HostStage hs;
-  if (!dev) {
-    if (c->comm.ev_end_set && (rc = comm_wait(c, c->comm.ev_end, "the previous sharded call")))
-      return rc;
-    const int rb[2] = {32, 4};
-    if ((rc = host_stage(c, n, rb, nreg, fk_err != nullptr, b_work, &hs, &work))) return rc;
-    if ((rc = host_points_in(c, P, pts, hs.pts))) return rc;
-    dp = reinterpret_cast<const double *>(hs.pts);
-    R[0].out = hs.out[0];
-    if (iters) R[1].out = hs.out[1];
-    dfk = reinterpret_cast<double *>(hs.fk);
-  } else {
-    if ((rc = ensure_scratch(c, b_work))) return rc;
-    work = static_cast<char *>(c->scratch);
-  }
+  const char *who = "ik_fabrik_solve_sharded";
+  if (const int rc = sharded_refusals(c, who, flags, pts, n, ang, max_iter >= 0)) return rc;
+  const ShardCall s = {who, IK_METHOD_FABRIK, pts, n, flags, stats, iters ? 2 : 1, {32, 4},
+                       {ang, iters}, fk_err, fabrik_scratch_bytes};
   const bool limits = !(flags & IK_F_NO_LIMITS);
-  rc = sharded_run(c, IK_METHOD_FABRIK, P, R, nreg, dfk, [&](const PartJob &j) {
-    return fabrik_launch(c, dp + 3 * j.b, j.m, tol, max_iter, reinterpret_cast<double *>(j.at[0]),
-                         iters ? reinterpret_cast<int32_t *>(j.at[1]) : nullptr, nullptr,
-                         j.fk_err, limits, work, j.S);
+  return sharded_call(c, s, [&](const PartJob &j, const double *p, void *work) {
+    return fabrik_launch(c, p, j.m, tol, max_iter, reinterpret_cast<double *>(j.at[0]),
+                         reinterpret_cast<int32_t *>(j.at[1]), nullptr, j.fk_err, limits, work,
+                         j.S);
   });
-  if (rc) return rc;
-  if (!dev) {
-    if ((rc = comm_wait(c, c->comm.ev_end, "the sharded call"))) return rc;
-    char *ho[2] = {reinterpret_cast<char *>(ang), reinterpret_cast<char *>(iters)};
-    if ((rc = host_results_out(c, P, R, nreg, ho, hs.fk, fk_err))) return rc;
-  }
-  if (flags & IK_F_ASYNC) return IK_OK;
-  return sharded_stats(c, stats);
 }
 
 }  // extern "C"

@@ -349,3 +349,247 @@ def test_stalled_gather_times_out_with_rccl_error():
         assert 1.9 <= secs <= 15.0, (mode, secs)
         assert "rank 0 of 2" in msg and "did not complete within 2 s" in msg, msg
         assert res[mode + "_refused"] and res[mode + "_after"], (mode, res)
+
+
+def _refusal_worker(q):
+    """The sharded entry points' refusals through ctx.lib (the Python wrappers
+    check arguments themselves): each alone, then two at a time -- the earlier
+    one's message is the one reported -- on a loopback communicator of one rank,
+    so that the valid calls at the end equal a plain solve."""
+    import ctypes
+    import torch
+    from inversekinematicsann_amd import _native as N
+    from inversekinematicsann_amd import dist as D
+    from inversekinematicsann_amd.kinematics.ann import (REFERENCE_X_SCALER as XS,
+                                                         REFERENCE_Y_SCALER as YS, glorot_model)
+    from inversekinematicsann_amd.robot.position_generator import random_dist
+    try:
+        bad, seen = [], 0
+        ctx, bare = N.Context(0), N.Context(0)  # bare: never gets a model
+        m = glorot_model(dims=(3, 64, 64, 4), seed=4)
+        ctx.ann_load(m.weights, m.biases, m.activations, XS.mean, XS.scale, YS.mean, YS.scale)
+        lib = ctx.lib
+        pts = random_dist(10, seed=7)
+        dpts = torch.from_numpy(pts).cuda()
+        f64 = torch.full((12, 4), 7.0, dtype=torch.float64, device="cuda")
+        f32 = torch.full((12, 4), 7.0, dtype=torch.float32, device="cuda")
+        h64, h32 = np.full((10, 4), 7.0), np.full((10, 4), 7.0, np.float32)
+        DEV, ASYNC = N.IK_F_DEVICE, N.IK_F_ASYNC
+        NOCOMM, NEEDS_DEV = "no communicator (ik_comm_init)", "IK_F_ASYNC requires IK_F_DEVICE"
+        BADARGS, ALIGN, NOMODEL = "bad args", "device ang must be 16-byte aligned", "no model loaded"
+
+        def call(c, who, p, n, ang, flags, max_iter=100):
+            st = N.IkStats()
+            if who == "ik_ann_solve_sharded":
+                return lib.ik_ann_solve_sharded(c.handle, p, n, ang, None, flags, ctypes.byref(st))
+            return lib.ik_fabrik_solve_sharded(c.handle, p, n, 1e-3, max_iter, ang, None, None,
+                                               flags, ctypes.byref(st))
+
+        def refused(label, c, who, code, text, *a, **kw):
+            nonlocal seen
+            seen += 1
+            rc, msg = call(c, who, *a, **kw), lib.ik_last_error().decode()
+            if rc != code or msg != who + ": " + text:
+                bad.append((label, who, rc, msg))
+
+        entries = (("ik_fabrik_solve_sharded", f64, h64), ("ik_ann_solve_sharded", f32, h32))
+        for who, d, h in entries:  # no communicator yet
+            refused("no comm", ctx, who, N.IK_E_BADARG, NOCOMM, N._ptr(pts), 10, N._ptr(h), 0)
+            refused("no comm + async", ctx, who, N.IK_E_BADARG, NOCOMM, N._ptr(pts), 10, N._ptr(h),
+                    ASYNC)
+        sc, sb = D.ShardedContext.loopback(ctx, 1, 0), D.ShardedContext.loopback(bare, 1, 0)
+        for who, d, h in entries:
+            hp, ha, dp, da = N._ptr(pts), N._ptr(h), dpts.data_ptr(), d.data_ptr()
+            refused("async", ctx, who, N.IK_E_BADARG, NEEDS_DEV, hp, 10, ha, ASYNC)
+            refused("n -1", ctx, who, N.IK_E_BADARG, BADARGS, hp, -1, ha, 0)
+            refused("n 2^48", ctx, who, N.IK_E_BADARG, BADARGS, hp, 1 << 48, ha, 0)
+            refused("NULL pts", ctx, who, N.IK_E_BADARG, BADARGS, None, 1, ha, 0)
+            refused("ang 8 mod 16", ctx, who, N.IK_E_BADARG, ALIGN, dp, 1, da + 8, DEV)
+            refused("async + n -1", ctx, who, N.IK_E_BADARG, NEEDS_DEV, hp, -1, ha, ASYNC)
+            refused("n -1 + ang", ctx, who, N.IK_E_BADARG, BADARGS, dp, -1, da + 8, DEV)
+        who, d, h = entries[0]
+        refused("max_iter -1", ctx, who, N.IK_E_BADARG, BADARGS, N._ptr(pts), 10, N._ptr(h), 0,
+                max_iter=-1)
+        who, d, h = entries[1]
+        refused("no model", bare, who, N.IK_E_NOMODEL, NOMODEL, N._ptr(pts), 10, N._ptr(h), 0)
+        refused("ang + no model", bare, who, N.IK_E_BADARG, ALIGN, dpts.data_ptr(), 1,
+                d.data_ptr() + 8, DEV)
+        st = N.IkStats()
+        null = (lib.ik_ann_solve_sharded(None, N._ptr(pts), 10, N._ptr(h32), None, 0, ctypes.byref(st)),
+                lib.ik_fabrik_solve_sharded(None, N._ptr(pts), 10, 1e-3, 100, N._ptr(h64), None, None,
+                                            0, ctypes.byref(st)))
+        # nothing was planned or launched: no chunk count recorded, no output written
+        torch.cuda.synchronize()
+        untouched = bool((f64 == 7.0).all() and (f32 == 7.0).all() and (h64 == 7.0).all()
+                         and (h32 == 7.0).all())
+        infos = (sc.info(), sb.info())
+        r_ang, r_it, _, _ = ctx.fabrik_solve(pts, 1e-3, 100)
+        a_ref, _, _ = ctx.ann_solve(pts)
+        ang, it, _, _ = sc.fabrik(pts, 1e-3, 100)
+        aang, _, _ = sc.ann(pts)
+        after = bool(np.array_equal(ang, r_ang) and np.array_equal(it, r_it)
+                     and np.array_equal(aang, a_ref))
+        sc.close()
+        sb.close()
+        q.put({"bad": bad, "seen": seen, "null": null, "untouched": untouched, "infos": infos,
+               "after": after})
+    except Exception as e:  # noqa: BLE001
+        import traceback
+        q.put(repr(e) + traceback.format_exc())
+
+
+def test_sharded_refusals_keep_their_order():
+    """Both entry points refuse in one order -- NULL context, no communicator,
+    IK_F_ASYNC without IK_F_DEVICE, the entry point's bad args (n < 0, n >= 2^48,
+    NULL pts, FABRIK max_iter < 0), a misaligned device ang, ANN without a model --
+    each with its own code and message, and of two refusals the earlier one's is
+    reported.  None of them plans or launches anything, and a valid call after
+    them equals the plain solve."""
+    from inversekinematicsann_amd import _native
+    res = _spawn(_refusal_worker, timeout=120)
+    assert not res["bad"], res["bad"]
+    assert res["seen"] == 2 * 2 + 2 * 7 + 3
+    assert res["null"] == (_native.IK_E_BADARG, _native.IK_E_BADARG)
+    assert res["untouched"]
+    assert res["infos"] == ((1, 0, 0), (1, 0, 0)), res["infos"]
+    assert res["after"]
+
+
+def _optional_outputs_worker(q):
+    """The sharded calls with every choice of optional outputs (FABRIK iters and
+    fk_err, ANN fk_err), through host pointers and IK_F_DEVICE tensors pre-filled
+    with a sentinel, as every rank of a loopback communicator: the chunk plans
+    with a ragged staged chunk, none, everything staged with an empty part, and
+    the empty batch.  iters == NULL with host pointers goes through ctx.lib (the
+    wrapper always passes iters)."""
+    import ctypes
+    import torch
+    from inversekinematicsann_amd import _native as N
+    from inversekinematicsann_amd import dist as D
+    from inversekinematicsann_amd.kinematics.ann import (REFERENCE_X_SCALER as XS,
+                                                         REFERENCE_Y_SCALER as YS, glorot_model)
+    from inversekinematicsann_amd.robot.position_generator import random_dist
+    try:
+        ctx = N.Context(0)
+        lib = ctx.lib
+        allpts = random_dist(258, seed=11)
+        m = glorot_model(dims=(3, 64, 64, 4), seed=4)
+        ctx.ann_load(m.weights, m.biases, m.activations, XS.mean, XS.scale, YS.mean, YS.scale)
+        bad, seen = [], 0
+
+        def check(what, ok):
+            nonlocal seen
+            seen += 1
+            if not ok:
+                bad.append(what)
+
+        def stats_agree(a, b):
+            a, b = a.as_dict(), b.as_dict()
+            exact = [k for k in a if k not in ("gather_ms", "sum_fk_err")]
+            return ({k: a[k] for k in exact} == {k: b[k] for k in exact}
+                    and abs(a["sum_fk_err"] - b["sum_fk_err"]) <= 1e-9 * max(1.0, b["sum_fk_err"]))
+
+        for n, g, chunks in ((257, 2, 3), (258, 2, 3), (2, 3, 1), (0, 2, 1)):
+            p = allpts[:n]
+            f_ang, f_it, f_err, _ = ctx.fabrik_solve_fk(p, 1e-3, 100)
+            a_ang, a_err, _ = ctx.ann_solve(p, want_fk_err=True)
+            dpts = torch.from_numpy(p).cuda()
+            C, _, _ = D.plan_of(n, g, chunks)
+            for r in range(g):
+                sc = D.ShardedContext.loopback(ctx, g, r)
+                sc.set_chunks(chunks)
+                own = np.zeros(n, bool)
+                for c in range(C):
+                    b, e = D.part_bounds(n, g, chunks, r, c)
+                    own[b:e] = True
+                x_ang = D.loopback_expected(n, g, r, chunks, 32, f_ang)
+                x_it = D.loopback_expected(n, g, r, chunks, 4, f_it)
+                x_aang = D.loopback_expected(n, g, r, chunks, 16, a_ang)
+
+                def errs_ok(err, ref, elsewhere):
+                    rest = err[~own]
+                    return bool(np.array_equal(err[own], ref[own], equal_nan=True) and
+                                (np.isnan(rest).all() if np.isnan(elsewhere)
+                                 else (rest == elsewhere).all()))
+
+                for w_it in (True, False):
+                    for w_fk in (True, False):
+                        tag = ("fabrik", n, g, chunks, r, w_it, w_fk)
+                        hst = N.IkStats()
+                        if w_it:
+                            ang, it, err, hst = sc.fabrik(p, 1e-3, 100, want_fk_err=w_fk)
+                            else_h = float("nan")
+                        else:
+                            ang, it = np.full((n, 4), 7.0), np.full(n, -9, np.int32)
+                            err = np.full(n, -1.0)
+                            ctx._check(lib.ik_fabrik_solve_sharded(
+                                ctx.handle, N._ptr(p), n, 1e-3, 100, N._ptr(ang), None,
+                                N._ptr(err) if w_fk else None, 0, ctypes.byref(hst)))
+                            else_h = -1.0
+                            check(tag + ("host iters untouched",), bool((it == -9).all()))
+                            if not w_fk:
+                                check(tag + ("host fk_err untouched",), bool((err == -1.0).all()))
+                        check(tag + ("info",), sc.info() == (g, r, chunks))
+                        dang = torch.full((n, 4), 7.0, dtype=torch.float64, device="cuda")
+                        dit = torch.full((n,), -9, dtype=torch.int32, device="cuda")
+                        derr = torch.full((n,), -1.0, dtype=torch.float64, device="cuda")
+                        dst = sc.fabrik_device(dpts, dang, dit if w_it else None,
+                                               derr if w_fk else None, 1e-3, 100)
+                        h_ang = np.ascontiguousarray(ang).view(np.uint8).reshape(n, 32)
+                        d_ang = dang.cpu().numpy().view(np.uint8).reshape(n, 32)
+                        check(tag + ("host ang",), np.array_equal(h_ang, x_ang))
+                        check(tag + ("device ang = host ang",), np.array_equal(d_ang, h_ang))
+                        d_it, d_err = dit.cpu().numpy(), derr.cpu().numpy()
+                        if w_it:
+                            h_it = it.view(np.uint8).reshape(n, 4)
+                            check(tag + ("host iters",), np.array_equal(h_it, x_it))
+                            check(tag + ("device iters = host iters",),
+                                  np.array_equal(d_it.view(np.uint8).reshape(n, 4), h_it))
+                        else:
+                            check(tag + ("device iters untouched",), bool((d_it == -9).all()))
+                        if w_fk:
+                            check(tag + ("host fk_err",), errs_ok(err, f_err, else_h))
+                            check(tag + ("device fk_err",), errs_ok(d_err, f_err, -1.0))
+                        else:
+                            check(tag + ("device fk_err untouched",), bool((d_err == -1.0).all()))
+                        check(tag + ("stats",), stats_agree(dst, hst))
+                        check(tag + ("info",), sc.info() == (g, r, chunks))
+                for w_fk in (True, False):
+                    tag = ("ann", n, g, chunks, r, w_fk)
+                    ang, err, hst = sc.ann(p, want_fk_err=w_fk)
+                    dang = torch.full((n, 4), 7.0, dtype=torch.float32, device="cuda")
+                    derr = torch.full((n,), -1.0, dtype=torch.float64, device="cuda")
+                    dst = sc.ann_device(dpts, dang, derr if w_fk else None)
+                    h_ang = ang.view(np.uint8).reshape(n, 16)
+                    check(tag + ("host ang",), np.array_equal(h_ang, x_aang))
+                    check(tag + ("device ang = host ang",), np.array_equal(
+                        dang.cpu().numpy().view(np.uint8).reshape(n, 16), h_ang))
+                    d_err = derr.cpu().numpy()
+                    if w_fk:
+                        check(tag + ("host fk_err",), errs_ok(err, a_err, float("nan")))
+                        check(tag + ("device fk_err",), errs_ok(d_err, a_err, -1.0))
+                    else:
+                        check(tag + ("host fk_err absent",), err is None)
+                        check(tag + ("device fk_err untouched",), bool((d_err == -1.0).all()))
+                    check(tag + ("stats",), stats_agree(dst, hst))
+                    check(tag + ("info",), sc.info() == (g, r, chunks))
+                sc.close()
+        q.put({"bad": bad, "seen": seen})
+    except Exception as e:  # noqa: BLE001
+        import traceback
+        q.put(repr(e) + traceback.format_exc())
+
+
+def test_sharded_optional_outputs_host_and_device():
+    """Every choice of the optional outputs, host pointers against device
+    tensors, at each rank of (n 257, g 2, 3 chunks: S = 43, two whole chunks and a
+    ragged third of 85 rows through the stage), (258, 2, 3: nothing staged), (2,
+    3, 1: everything staged, rank 2's part empty) and (0, 2, 1: the tail-only
+    exchange): the gathered arrays are dist.loopback_expected of a plain solve
+    byte for byte and the same bytes either way, fk_err holds the plain solve's
+    values on this rank's rows and the pre-fill elsewhere (the device tensor's
+    sentinel, the wrapper's NaN), an absent output's buffer is untouched, the
+    stats of the two calls agree and info() reports the chunk setting."""
+    res = _spawn(_optional_outputs_worker, timeout=200)
+    assert not res["bad"], res["bad"][:20]
+    assert res["seen"] > 9 * 4 * 6
