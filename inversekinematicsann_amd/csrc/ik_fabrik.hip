@@ -16,38 +16,13 @@
 //    joints never touch HBM.
 //  * simple: everything in one kernel, one point per lane, no refill.
 // Per point the state is 4 joints + goal (15 doubles) held in VGPRs.
+#include <algorithm>
 #include <cmath>
 
 #include "ik_common.h"
 #include "ik_fabrik_step.h"
 
 namespace ikhip {
-
-// div_core's domain for the link lengths (the numerators): 2^-100 <= |L| <= 2^100.
-static bool links_core_ok(const double *L, int n) {
-  for (int k = 0; k < n; ++k) {
-    const double v = std::fabs(L[k]);
-    if (!(v >= 0x1p-100 && v <= 0x1p100)) return false;
-  }
-  return true;
-}
-
-// The largest x with fl(sqrt(x)) <= tol (NaN for a NaN tol, -inf for a
-// negative one), so that the reference's `sqrt(x) > tol` is `x > t` bit for
-// bit.  The loop's initial errors of 1.0 stay 1.0 (sqrt(1) = 1 exactly).
-static double tol_threshold(double tol) {
-  if (std::isnan(tol)) return NAN;
-  if (tol < 0) return -INFINITY;
-  if (std::isinf(tol)) return INFINITY;
-  double t = tol * tol;
-  while (std::sqrt(t) > tol) t = std::nextafter(t, -INFINITY);
-  for (;;) {
-    const double u = std::nextafter(t, INFINITY);
-    if (std::sqrt(u) <= tol) t = u;
-    else break;
-  }
-  return t;
-}
 
 // kinematics/inverse.py:54-112 __get_angles; J = FABRIK joints B, C, D, E.
 __device__ __forceinline__ void get_angles(const d3 J[4], double th[4], int &st) {
@@ -270,14 +245,6 @@ __device__ __forceinline__ bool get_angles_core(const d3 J[4], double th[4], int
   return ok && dom < kCoreDom;
 }
 
-// Seed pose, inverse.py:123-130: FK of [atan2(y, x), thetas[1:]] (the
-// reference writes theta_1 into dh_matrix[0][0] and runs fkine on that row), in
-// closed form from the per-robot constants (seed_closed, ik_common.h; r05 and
-// before: seed_chain, the DH chain's own products).
-__device__ __forceinline__ int seed_pose(const RobotConstDev *rc, d3 g, d3 J[4]) {
-  return seed_closed(rc, g, J);
-}
-
 // The per-robot constants (RobotConstDev).  jc / alpha_bad come from the host
 // (fk_trip_consts: the values the ANN kernel's round trip uses too).
 struct FkTrip {
@@ -389,9 +356,7 @@ static int env_int(const char *name, int dflt) {
   return (v && *v) ? atoi(v) : dflt;
 }
 
-// The angles step of one finished point (inverse.py:136 __get_angles) and what
-// the call reports about it: angles, iterations, joints, the FK round trip
-// (cli.py:54-61) and the per-lane sums of the batch stats.
+// A lane's sums of the batch stats over the points it committed (commit_point).
 struct LaneAcc {
   unsigned long long sum_it = 0, capped = 0;
   int max_it = 0;
@@ -504,7 +469,11 @@ __global__ __launch_bounds__(256) void fabrik_simple_kernel(FabArgs a) {
     g = {a.pts[3 * i], a.pts[3 * i + 1], a.pts[3 * i + 2]};
     if (a.check_limits && outside(a.r.lim, g.x, g.y, g.z))
       atomicMin(&a.S->first_oob, (unsigned long long)i);
-    st = seed_pose(a.rc, g, J);
+    // Seed pose, inverse.py:123-130: FK of [atan2(y, x), thetas[1:]] (the
+    // reference writes theta_1 into dh_matrix[0][0] and runs fkine on that row), in
+    // closed form from the per-robot constants (seed_closed, ik_common.h; r05 and
+    // before: seed_chain, the DH chain's own products).
+    st = seed_closed(a.rc, g, J);
     double se = 1.0, ge = 1.0;
     if (st == IK_OK) {
       while (((se > a.tol2) || (ge > a.tol2)) && (a.max_iter > it)) {
@@ -527,10 +496,11 @@ __global__ __launch_bounds__(256) void fabrik_simple_kernel(FabArgs a) {
 // The whole FABRIK solve of one goal in the general arithmetic (the simple
 // kernel's loop: fabrik.py:44-67 from the seed pose, inverse.py:123-133): the
 // iteration kernel's retire step re-solves the rare lanes whose core sequences
-// left their domain (kStRedo) with it.
+// left their domain (kStRedo) with it.  (The simple kernel keeps its own copy of
+// the loop: with a call of this function the compiler emits other code for it.)
 __device__ __forceinline__ void solve_general(const FabArgs &a, d3 g, d3 J[4], int &it,
                                               int &st) {
-  st = seed_pose(a.rc, g, J);
+  st = seed_closed(a.rc, g, J);
   it = 0;
   double se = 1.0, ge = 1.0;
   if (st != IK_OK) return;
@@ -1145,7 +1115,7 @@ fabrik_iter_kernel(FabArgs a) {
           if (a.check_limits && outside_rc(k, ng))
             atomicMin(&a.S->first_oob, (unsigned long long)ni);
           d3 Js[4];
-          (void)seed_pose((const RobotConstDev *)k, ng, Js);
+          (void)seed_closed((const RobotConstDev *)k, ng, Js);
           uint64_t meta = (uint64_t)ni;
           double pcq = 0.0;
           if constexpr (CORE == 2) {
@@ -1356,6 +1326,25 @@ void launch_fabrik_ikine(const RobotDev &r, const double *pts, int64_t n, double
                          const RobotConstDev *rc, unsigned long long *dbg, int bpc_req,
                          bool prior) {
   if (n <= 0) return;
+  // every decision of the launch (ik_fabrik_plan.cpp); the environment is read once
+  static const int order_on = env_int("IKHIP_FABRIK_ORDER", 1);
+  static const int chunk = env_int("IKHIP_FABRIK_CHUNK", 64);
+  FabPlanIn in;
+  std::copy(r.dh, r.dh + 16, in.dh);
+  std::copy(r.links, r.links + 4, in.links);
+  in.n = n;
+  in.tol = tol;
+  in.max_iter = max_iter;
+  in.variant = variant;
+  in.core_req = core_req;
+  in.bpc_req = bpc_req;
+  in.has_table = ord != nullptr;
+  in.order_env = order_on;
+  in.chunk_env = chunk;
+  in.cus = num_cus();
+  in.ord_ppt = kOrdPPT;
+  in.iter_waves = kIterWaves;
+  const FabPlan p = fabrik_plan(in);
   FabArgs a;
   a.r = r;
   a.rc = rc;
@@ -1363,16 +1352,10 @@ void launch_fabrik_ikine(const RobotDev &r, const double *pts, int64_t n, double
   a.pts = pts;
   a.n = n;
   a.tol = tol;
-  a.tol2 = tol_threshold(tol);
-  // the band covers goals well past the reach: 64 (1 + |d1| + |a1| + sum L)
-  {
-    const double sum_l = std::fabs(r.links[0]) + std::fabs(r.links[1]) + std::fabs(r.links[2]) +
-                         std::fabs(r.links[3]);
-    a.band_n1 = 64.0 * (1.0 + std::fabs(r.dh[4]) + std::fabs(r.dh[8]) + sum_l);
-    if (!std::isfinite(a.band_n1)) a.band_n1 = -1.0;  // (no lane: every comparison exact)
-    a.band = fabrik_band(a.tol2, a.band_n1, sum_l);
-    a.qmax = fabrik_qmax(r.links);
-  }
+  a.tol2 = p.tol2;
+  a.band = p.band;
+  a.band_n1 = p.band_n1;
+  a.qmax = p.qmax;
   a.max_iter = max_iter;
   a.check_limits = check_limits ? 1 : 0;
   a.ang = ang;
@@ -1380,79 +1363,42 @@ void launch_fabrik_ikine(const RobotDev &r, const double *pts, int64_t n, double
   a.joints = joints;
   a.fk_err = fk_err;
   a.S = S;
-  a.chunk = 64;
+  a.chunk = p.chunk;
   a.perm = nullptr;
   a.cell = nullptr;
   a.ord = ord;
   a.prior_gate = prior ? 1 : 0;
-  // the seed's own angles (robot_const_kernel's check, forward.py:23-25)
-  bool robot_ok = true;
-  for (int k = 1; k < 4; ++k)
-    if (r.dh[k] < -2 * kPi || r.dh[k] > 2 * kPi) robot_ok = false;
-  for (int k = 0; k < 4; ++k)
-    if (r.dh[12 + k] < -2 * kPi || r.dh[12 + k] > 2 * kPi) robot_ok = false;
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  // no iteration at all when the loop's initial errors of 1.0 already pass
-  if (variant == 0 || max_iter <= 0 || !(1.0 > a.tol2) || !robot_ok) {
+  if (p.simple) {
     kt_begin("fabrik_simple_kernel", stream);
-    IK_LAUNCH(fabrik_simple_kernel, dim3(grid), dim3(256), 0, stream, a);
+    IK_LAUNCH(fabrik_simple_kernel, dim3(p.grid), dim3(256), 0, stream, a);
     kt_end(stream);
     return;
   }
-  static const int order_on = env_int("IKHIP_FABRIK_ORDER", 1);
-  const bool ordered = ord && order_on && n < (int64_t)1 << 31;
-  if (ordered) {
-    char *p = static_cast<char *>(scratch);
-    const unsigned ogrid = (unsigned)((n + 256 * kOrdPPT - 1) / (256 * kOrdPPT));
-    a.perm = reinterpret_cast<int32_t *>(p);
-    p += up256((size_t)n * 4);
-    a.cell = reinterpret_cast<uint16_t *>(p);
+  if (p.ordered) {
+    char *sp = static_cast<char *>(scratch);
+    a.perm = reinterpret_cast<int32_t *>(sp);
+    sp += up256((size_t)n * 4);
+    a.cell = reinterpret_cast<uint16_t *>(sp);
     kt_begin("fabrik_classify_kernel", stream);
-    IK_LAUNCH(fabrik_classify_kernel, dim3(ogrid), dim3(256), 0, stream, a);
+    IK_LAUNCH(fabrik_classify_kernel, dim3(p.ogrid), dim3(256), 0, stream, a);
     kt_end(stream);
     kt_begin("fabrik_scatter_kernel", stream);
-    IK_LAUNCH(fabrik_scatter_kernel, dim3(ogrid), dim3(256), 0, stream, a);
+    IK_LAUNCH(fabrik_scatter_kernel, dim3(p.ogrid), dim3(256), 0, stream, a);
     kt_end(stream);
   }
-  // persistent grid: blocks_per_cu 256-thread blocks per CU (= waves per SIMD)
-  // measured on MI355X (tools/sweep_fabrik.py): at 1M points 2 blocks/CU with
-  // 64-point grabs beats 4 and 8 by 10-30 % (more lanes = fewer points per lane
-  // = a longer divergent tail); 2 and 3 are within noise at 1-1.25M points, and
-  // from 4M points on 3 wins by ~5 % at every tolerance (the tail matters less
-  // than the latency a third wave per SIMD hides), and so it does at 1M points
-  // with tol 1e-5 (56 iterations per point against 33 at 1e-3).
-  // (4M / 10M points at tol 1e-3: 4 per CU is 2 % ahead of 3; at 1e-5 they are even)
-  // bpc_req: the context's IKHIP_FABRIK_BPC (0 = this rule)
-  // The fused kernel keeps the batch of prepared points and the angles step's
-  // temporaries beside the loop state: ~250 VGPRs, two waves per SIMD at most.
-  const int bpc = bpc_req > 0 ? (bpc_req < kIterWaves ? bpc_req : kIterWaves) : kIterWaves;
-  static const int chunk = env_int("IKHIP_FABRIK_CHUNK", 64);
-  a.chunk = (chunk > 0 && chunk <= 64) ? chunk : 64;
-  unsigned pgrid = (unsigned)num_cus() * (unsigned)(bpc > 0 ? bpc : 8);
-  int64_t waves_needed = (n + 63) / 64;
-  if ((int64_t)pgrid * 4 > waves_needed)
-    pgrid = (unsigned)((waves_needed + 3) / 4 > 0 ? (waves_needed + 3) / 4 : 1);
-  // the iteration through sqrt_core / div_core (same bits, fewer instructions)
-  // unless the link lengths are outside div_core's domain, and with the repeated
-  // distances taken once (core 2) when L0 == L1 and L2 == L3.  core_req (context's
-  // IKHIP_FABRIK_CORE) 0 forces the general sqrt / division, 1 the core sequences
-  // without the reuse.
-  const double *Lk = a.r.links;
-  int core = links_core_ok(Lk, 4) ? core_req : 0;
-  if (core == 2 && !(Lk[0] == Lk[1] && Lk[2] == Lk[3])) core = 1;
 #ifdef IKHIP_DIAG
   if (a.dbg) (void)hipMemsetAsync(a.dbg, 0, kFabrikDebugWords * 8, stream);
 #endif
   kt_begin("fabrik_iter_kernel", stream);
-  if (variant == 2) {
-    if (ordered) launch_iter<1, true>(core, pgrid, stream, a);
-    else launch_iter<1, false>(core, pgrid, stream, a);
+  if (p.refill1) {
+    if (p.ordered) launch_iter<1, true>(p.core, p.pgrid, stream, a);
+    else launch_iter<1, false>(p.core, p.pgrid, stream, a);
   } else {
-    if (ordered) launch_iter<IKHIP_FAB_REFILL, true>(core, pgrid, stream, a);
-    else launch_iter<IKHIP_FAB_REFILL, false>(core, pgrid, stream, a);
+    if (p.ordered) launch_iter<IKHIP_FAB_REFILL, true>(p.core, p.pgrid, stream, a);
+    else launch_iter<IKHIP_FAB_REFILL, false>(p.core, p.pgrid, stream, a);
   }
   kt_end(stream);
-  if (ordered) {
+  if (p.ordered) {
     kt_begin("fabrik_fold_kernel", stream);
     IK_LAUNCH(fabrik_fold_kernel, dim3(1), dim3(256), 0, stream, a);
     kt_end(stream);

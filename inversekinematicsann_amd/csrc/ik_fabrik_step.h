@@ -5,6 +5,7 @@
 #pragma once
 
 #include "ik_common.h"
+#include "ik_fabrik_plan.h"
 
 namespace ikhip {
 
@@ -123,44 +124,22 @@ namespace ikhip {
 //   sea > hi = (D + T) (1 + 2^-36)        =>  se2 > tol2
 //   sea < lo = (T - D) (1 - 2^-36)        =>  se2 <= tol2   (only if D <= T / 2)
 // (tests/test_band_cpu.py checks the bound along real iterations.)  The band is one
-// per launch (fabrik_band on the host): n1max bounds |start|_1 + |goal|_1 (L1 norms
-// bound the Euclidean ones), with T's bounds tol_lo <= T <= tol_hi.  A lane past
+// per launch (fabrik_band, on the host: ik_fabrik_plan.cpp): n1max bounds
+// |start|_1 + |goal|_1 (L1 norms bound the Euclidean ones), with T's bounds
+// tol_lo <= T <= tol_hi.  A lane past
 // n1max (or with a non-finite goal) never runs this step: the iteration kernel hands
 // it to the retire step's general re-solve (r06; r05 made its comparisons exact).
-struct ErrBand {
-  double lo, hi;
-};
-
-__host__ __forceinline__ ErrBand fabrik_band(double tol2, double n1max, double sum_l) {
-  // tol2 <= 0 (tol = 0, or a negative tol): a band that decides nothing, every
-  // comparison exact.  (hi = 0 would call any sea > 0 "above", but at tol = 0 the
-  // reference stops where b0 rounds onto start exactly, se2 == 0, while s is
-  // L0 +- 1 ulp and sea > 0: ADVICE r05.)
-  ErrBand b = {-1.0, INFINITY};
-  if (!(tol2 > 0.0)) return b;
-  const double T = std::sqrt(tol2);
-  const double tol_lo = T * (1.0 - 0x1p-50), tol_hi = T * (1.0 + 0x1p-50);
-  const double d = 0x1p-52 * (6.0 * n1max + 8.0 * sum_l + 1.0);
-  b.hi = (d + tol_hi) * (1.0 + 0x1p-36);
-  b.lo = (d <= 0.5 * tol_lo) ? (tol_lo - d) * (1.0 - 0x1p-36) : -1.0;
-  return b;
-}
 
 // The core domain from the quotients (r06): a radicand x outside sqrt_core's
 // domain (0, tiny, inf, NaN) gives a quotient L / sqrt_core(x) that is NaN or
 // larger in magnitude than |L| 2^382 (tools/dom_check.hip, every binade below
 // 2^-767 and the specials on gfx950), and an in-domain one a quotient at most
-// |L| 2^383.5.  So |q1| + |q| + |q2| + |cq| <= qmax = min |L| 2^382 (fabrik_qmax)
-// implies every radicand of the iteration is >= 2^-764 and finite: in the
+// |L| 2^383.5.  So |q1| + |q| + |q2| + |cq| <= qmax = min |L| 2^382 (fabrik_qmax,
+// on the host: ik_fabrik_plan.cpp) implies every radicand of the iteration is >= 2^-764 and finite: in the
 // domain.  Lanes that fail it (the true out-of-domain ones and any in
 // [2^-767, 2^-764)) are re-solved in the general arithmetic (kStRedo): the same
 // bits either way.  3 adds and a compare instead of four exponent extractions,
 // their maximum and a compare.
-__host__ __forceinline__ double fabrik_qmax(const double *L) {
-  double m = std::fabs(L[0]);
-  for (int k = 1; k < 4; ++k) m = std::fmin(m, std::fabs(L[k]));
-  return m * 0x1p382;
-}
 
 // fabrik_step4_reuse with the loop condition cont = (se2 > tol2) || (ge2 > tol2)
 // decided through the band, the core domain from the quotients, and F3 (c3 = c2 +

@@ -1,6 +1,6 @@
-"""The FABRIK loop condition's error band (csrc/ik_fabrik_step.h, fabrik_step4_lazy /
-fabrik_band), checked numerically on the CPU: along real FABRIK iterations (numpy
-float64, the reference's arithmetic: kinematics/point.py:25-45, fabrik.py:19-64),
+"""The FABRIK loop condition's error band (csrc/ik_fabrik_step.h, fabrik_step4_lazy;
+csrc/ik_fabrik_plan.cpp, fabrik_band), checked numerically on the CPU: along real
+FABRIK iterations (numpy float64, the reference's arithmetic: kinematics/point.py:25-45, fabrik.py:19-64),
 the start and goal errors the step approximates from its radicands' roots,
 |sqrt(x) - L0| and |sqrt(x3) - L3| (r06; r05: |1 - q| sqrt(x)), stay within the band's
 D of the reference's own
@@ -8,8 +8,16 @@ D of the reference's own
 comparison for thresholds placed right at the errors.  The GPU tests check the
 kernel bit for bit; this pins the bound the kernel's proof rests on, including the
 converged states where the errors are tiny and the approximation is all roundoff.
+band() below restates fabrik_band (csrc/ik_fabrik_plan.cpp); the check program
+tests/host/fabrik_plan_check.cpp prints the function's own results (--band), and
+band() must reproduce them bit for bit, so the experiments run on the source's band.
 """
+import math
+
 import numpy as np
+import pytest
+
+from tests.test_fabrik_plan_cpu import build_check, run_check
 
 U = 2.0 ** -53
 
@@ -23,7 +31,7 @@ def pb(s, e, d):
 
 
 def band(tol2, n1max, sum_l):
-    """fabrik_band (ik_fabrik_step.h), restated."""
+    """fabrik_band (ik_fabrik_plan.cpp), restated (test_band_restates_the_source)."""
     if not tol2 > 0.0:
         return -1.0, np.inf, 0.0  # decides nothing: every comparison exact
     T = np.sqrt(tol2)
@@ -32,6 +40,35 @@ def band(tol2, n1max, sum_l):
     hi = (d + thi) * (1.0 + 2.0 ** -36)
     lo = (tlo - d) * (1.0 - 2.0 ** -36) if d <= 0.5 * tlo else -1.0
     return lo, hi, d
+
+
+@pytest.fixture(scope="module")
+def plan_check(tmp_path_factory):
+    """The check program's verdict on ik_fabrik_plan.cpp (its own assertions all
+    held) and its --band lines: (tol2, n1max, sum_l, lo, hi) from fabrik_band itself."""
+    exe = build_check(tmp_path_factory.mktemp("fabrik_plan"))
+    assert "fabrik_plan_check ok" in run_check(exe)
+    rows = [tuple(float.fromhex(v) for v in line.split())
+            for line in run_check(exe, "--band").splitlines()]
+    assert len(rows) >= 30 and all(len(r) == 5 for r in rows)
+    return rows
+
+
+def test_band_restates_the_source(plan_check):
+    """band() gives fabrik_band's lo and hi bit for bit on the program's list: the
+    thresholds of tol 1e-3 / 1e-5 / 1e-13 (and others down to the smallest subnormal
+    and up to DBL_MAX), n1max of the default launch, of a small and a large robot and
+    -1 ("no lane"), and tol2 <= 0 / NaN."""
+    bits = lambda v: np.float64(v).tobytes()
+    n1s, decided, undecided = set(), 0, 0
+    for tol2, n1max, sum_l, lo, hi in plan_check:
+        plo, phi, _ = band(tol2, n1max, sum_l)
+        assert bits(plo) == bits(lo) and bits(phi) == bits(hi), (tol2.hex(), n1max, sum_l)
+        n1s.add(n1max)
+        decided += lo > 0.0
+        undecided += lo == -1.0
+    assert -1.0 in n1s and 64.0 * 11.0 in n1s
+    assert decided >= 10 and undecided >= 10  # both branches of lo
 
 
 def chains(n, rng):
@@ -113,21 +150,20 @@ def test_band_decisions_match_exact_comparisons():
     assert checked > 5000 and undecided > 1000
 
 
-def test_band_at_tol_zero_decides_nothing():
+def test_band_at_tol_zero_decides_nothing(plan_check):
     """tol = 0 (tol2 = 0): fabrik.py:57 stops only where both errors are exactly 0.
     A band with hi = 0 would call every lane with |1 - q| sqrt(x) > 0 "above tol",
     also one whose b0 rounds exactly onto start (se2 == 0) while q is an ulp off 1
     (not met on the trajectories below, where se2 == 0 comes with
     q == 1, but nothing rules it out).  fabrik_band returns (lo, hi) = (-1, inf)
-    for tol2 <= 0, so no lane is decided by it and every comparison is exact;
+    for tol2 <= 0 and NaN (asserted by the check program, and read off its --band lines
+    here), so no lane is decided by it and every comparison is exact;
     tests/test_gpu_parity.py::test_fabrik_tol_zero_and_negative checks the kernels."""
-    import re
-    src = open(__file__.replace("tests/test_band_cpu.py",
-                                "inversekinematicsann_amd/csrc/ik_fabrik_step.h")).read()
-    body = src[src.index("fabrik_band(double tol2"):]
-    assert re.search(r"ErrBand b = \{-1\.0, INFINITY\};\s*(//[^\n]*\n\s*)*"
-                     r"if \(!\(tol2 > 0\.0\)\) return b;", body[:800]), \
-        "fabrik_band must decide nothing for tol2 <= 0"
+    none = [r for r in plan_check if not r[0] > 0.0]  # tol2 in {0, -0.0, -1, -inf, NaN}
+    assert len(none) >= 5 and any(math.isnan(r[0]) for r in none)
+    assert {math.copysign(1.0, r[0]) for r in none if r[0] == 0.0} == {1.0, -1.0}
+    for r in none:
+        assert r[3] == -1.0 and r[4] == np.inf, "fabrik_band must decide nothing for tol2 <= 0"
     rng = np.random.default_rng(7)
     L = 2.0
     J, g = chains(4000, rng)
@@ -150,7 +186,7 @@ def test_band_at_tol_zero_decides_nothing():
     assert zero > 0  # converged chains do reach se2 == 0, where tol 0 can stop
 
 
-def test_quotient_domain_test_evidence():
+def test_quotient_domain_test_evidence(plan_check):
     """The iteration's core-domain test reads the quotients (ik_fabrik_step.h,
     fabrik_step4_lazy / fabrik_qmax, r06): |q1| + |q| + |q2| + |cq| <= min|L| 2^382.
     It is sound only if every radicand below sqrt_core's domain gives a quotient
@@ -158,7 +194,8 @@ def test_quotient_domain_test_evidence():
     v_rcp_f64 that no CPU can restate.  tools/dom_check.hip measured it on gfx950
     (2^30 radicands per link length over every binade below 2^-767, subnormals
     included, and 0 / inf / NaN); this pins the committed record and the source's
-    threshold."""
+    threshold: the check program (plan_check) asserts fabrik_qmax == min |L| 2^382
+    exactly, negative links and the minimum in every position included."""
     import json
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -174,5 +211,4 @@ def test_quotient_domain_test_evidence():
         assert r["radicands"] >= 2 ** 30
     assert any(abs(r["L"]) < 2.0 ** -90 for r in rows) and any(abs(r["L"]) > 2.0 ** 90 for r in rows)
     src = open(os.path.join(root, "inversekinematicsann_amd", "csrc", "ik_fabrik_step.h")).read()
-    assert "return m * 0x1p382;" in src
     assert "(fabs(q1) + fabs(q)) + (fabs(q2) + fabs(cq)) <= qmax" in src

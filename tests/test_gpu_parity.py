@@ -89,6 +89,30 @@ def test_fabrik_vs_oracle_tight_tolerances(ctx):
             assert np.abs(a_[ok] - r_[ok]).max() <= 1e-9
 
 
+def test_fabrik_launch_sequence():
+    """The launches the FABRIK plan (csrc/ik_fabrik_plan.cpp) decides, by the kernels'
+    names in launch order, at n = 257 (one point past a block): the fused pipeline
+    by default (a fresh context has the built-in cost table, so it orders), the simple
+    kernel where the loop runs no iteration (max_iter 0; tol 1: the initial errors
+    of 1.0 already pass), nothing at all for an empty batch."""
+    from inversekinematicsann_amd import _native
+    from inversekinematicsann_amd.robot.position_generator import random_dist
+    pts = random_dist(257, seed=23)
+    fused = ["fabrik_classify_kernel", "fabrik_scatter_kernel", "fabrik_iter_kernel",
+             "fabrik_fold_kernel"]
+    c = _native.Context(0)
+    try:
+        c.set_timing(True)
+        for p, tol, mi, want in ((pts, 1e-3, 100, fused),
+                                 (pts, 1e-3, 0, ["fabrik_simple_kernel"]),
+                                 (pts, 1.0, 100, ["fabrik_simple_kernel"]),
+                                 (pts[:0], 1e-3, 100, [])):
+            c.fabrik_solve(p, tol, mi)
+            assert [k for k, _ in c.kernel_times()] == want, (len(p), tol, mi)
+    finally:
+        c.close()
+
+
 def test_fabrik_tol_zero_and_negative():
     """tol = 0 (and tols whose threshold rounds to 0, or below it) is accepted by
     the reference (fabrik.py:57: the loop then stops only where both errors are

@@ -16,7 +16,8 @@
 //  kloop V      the fp16x3 layer's K loop alone, with / without its loads, and over
 //               a 12 MiB weight set (V 4; V 5 with each workgroup at its own layer).
 //
-// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -o tools/ubench tools/ubench.hip
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -o tools/ubench tools/ubench.hip \
+//          inversekinematicsann_amd/csrc/ik_fabrik_plan.cpp
 // Prints one JSON line per case: times from HIP events, cycles from s_memtime
 // (shader clock ticks) in block 0.
 #include <hip/hip_runtime.h>
@@ -446,7 +447,7 @@ static void timed(const char *name, F launch, unsigned long long *dclk, double w
 }
 
 int main(int argc, char **argv) {
-  const int cus = num_cus();
+  const int cus = ::num_cus();  // (ik_common.h has one of its own in ikhip::)
   double *dout = nullptr, *dgoals = nullptr;
   unsigned long long *dclk = nullptr;
   CK(hipMalloc(&dout, (size_t)cus * 8 * 256 * 8));
