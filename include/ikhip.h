@@ -45,7 +45,8 @@ typedef enum ik_status {
 enum {
   IK_F_DEVICE = 1,    /* array arguments are device pointers */
   IK_F_ASYNC = 2,     /* enqueue only; requires IK_F_DEVICE */
-  IK_F_NO_LIMITS = 4  /* skip the workspace check (ANN.predict has none, ann.py:70-76) */
+  IK_F_NO_LIMITS = 4, /* skip the workspace check (ANN.predict has none, ann.py:70-76) */
+  IK_F_PITCH_NEAREST = 8 /* ik_analytic_solve only: move an infeasible pitch to the nearest feasible */
 };
 
 enum { IK_ACT_LINEAR = 0, IK_ACT_TANH = 1, IK_ACT_RELU = 2, IK_ACT_SIGMOID = 3 };
@@ -202,6 +203,48 @@ int ik_refine(ik_ctx *ctx, const double *pts, const double *seed, int64_t n, dou
 int ik_ann_solve_refined(ik_ctx *ctx, const double *pts, int64_t n, double tol, int32_t max_iter,
                          double damping, double *ang, int32_t *iters, double *fk_err,
                          double *seed_fk_err, int flags, ik_stats *stats);
+
+/* ---- Analytic ----------------------------------------------------------------
+ * Closed-form inverse kinematics with a chosen tool pitch and elbow branch, float64,
+ * no iteration, for a context's robot that is a yaw joint followed by a planar
+ * three-link chain: |cos alpha1| <= 1e-12 and sin alpha1 > 0, alpha2..4 = 0,
+ * d2..4 = 0, a2 / a3 / a4 finite and > 0, a1 finite and >= 0 (SixDOFRobot is one;
+ * any other table is IK_E_BADARG naming the entry, and the context stays usable).
+ * With d1 = d[0], a1..a4 = a[0..3], per row, goal (x, y, z), elbow b = -1 / +1:
+ *   theta1 = atan2(y, x);  r = sqrt(x^2 + y^2) - a1;  h = z - d1
+ *   rho^2 = r^2 + h^2;  rho = sqrt(rho^2);  gamma = atan2(h, r)
+ *   phi = pitch ? pitch[i] : gamma   (the tool points away from the shoulder)
+ *   wrist(phi): wr = r - a4 cos phi;  wh = h - a4 sin phi;  W = sqrt(wr^2 + wh^2)
+ *     m = (a2 + a3 - W)(a2 + a3 + W) / (2 a2 a3)          (= 1 - cos theta3)
+ *     q = (W - |a2 - a3|)(W + |a2 - a3|) / (2 a2 a3)      (= 1 + cos theta3)
+ *   infeasible = !(m >= 0 and q >= 0): the row fails, unless IK_F_PITCH_NEAREST:
+ *     cmin = (rho^2 + a4^2 - (a2 + a3)^2) / (2 a4 rho)
+ *     cmax = (rho^2 + a4^2 - (a2 - a3)^2) / (2 a4 rho);  delta = wrap(phi - gamma)
+ *     the row fails when !(cmin <= 1 and cmax >= -1 and rho > 0), or when delta is
+ *     NaN (a NaN or infinite pitch has no nearest one); else
+ *     lo = acos(min(cmax, 1));  hi = acos(max(cmin, -1))
+ *     phi = gamma + sign(delta) clamp(|delta|, lo, hi)   (sign(0) = +1)
+ *     wrist(phi) again;  m = max(m, 0);  q = max(q, 0);  the row counts as moved
+ *   s3 = b sqrt(m q);  c3 = (q - m) / 2;  theta3 = b 2 atan2(sqrt(m), sqrt(q))
+ *   theta2 = atan2(wh, wr) - atan2(a3 s3, a2 + a3 c3);  theta4 = phi - theta2 - theta3
+ *   ang = (theta1, wrap(theta2), theta3, wrap(theta4)), wrap as in ik_refine.
+ * IK_ELBOW_UP gives theta3 <= 0, IK_ELBOW_DOWN theta3 >= 0 (the elbow below the
+ * shoulder-wrist line for alpha1 = +pi/2).  Only the front branch of theta1 is
+ * solved (r < 0, reaching over the back, is out of scope).
+ * pts n x 3, pitch (nullable) n, ang n x 4 (float64); pitch_out (nullable) n: the
+ * pitch used, bit-equal to pitch[i] on a row that was not moved; fk_err (nullable)
+ * n: |FK(ang) - p|_2 through the library's FK chain, at rounding level.  A failed
+ * row has ang, pitch_out and fk_err NaN.  stats: first_oob as for the other solves
+ * (unless IK_F_NO_LIMITS; the rows are still solved), first_err the lowest failed
+ * row with first_err_code = IK_E_OUT_OF_REACH, n_capped = rows whose pitch was
+ * moved, max_iters = sum_iters = 0, max_fk_err / sum_fk_err over the finite errors.
+ * IK_E_BADARG: a NULL context, n < 0, a NULL pts / ang with n > 0, elbow not -1 / +1,
+ * IK_F_ASYNC without IK_F_DEVICE, a device ang not 16-byte aligned, an unsupported
+ * robot.  n == 0 is IK_OK with empty stats whatever the arrays. */
+enum { IK_ELBOW_UP = -1, IK_ELBOW_DOWN = 1 };
+int ik_analytic_solve(ik_ctx *ctx, const double *pts, const double *pitch /*nullable: n*/,
+                      int64_t n, int elbow, double *ang /*n x 4*/, double *pitch_out /*nullable*/,
+                      double *fk_err /*nullable*/, int flags, ik_stats *stats);
 
 /* Arithmetic of the hidden-layer GEMMs.  IK_ANN_FP32 (default): fp32 MFMA
  * (v_mfma_f32_32x32x2_f32), a fp32 dot product like the reference's TF/Keras

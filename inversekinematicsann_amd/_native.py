@@ -27,13 +27,14 @@ IK_METHOD_ANN, IK_METHOD_FABRIK = 0, 1
 IK_COMM_ID_BYTES = 128
 IK_MAX_GATHER_CHUNKS = 8
 IK_FKHIST_BINS = 2048
-IK_F_DEVICE, IK_F_ASYNC, IK_F_NO_LIMITS = 1, 2, 4
+IK_F_DEVICE, IK_F_ASYNC, IK_F_NO_LIMITS, IK_F_PITCH_NEAREST = 1, 2, 4, 8
+IK_ELBOW_UP, IK_ELBOW_DOWN = -1, 1
 ACTS = {"linear": 0, "tanh": 1, "relu": 2, "sigmoid": 3}
 
 EXPORTED_SYMBOLS = ("ik_ctx_create", "ik_ctx_destroy", "ik_ctx_set_stream", "ik_ctx_get_stream",
                     "ik_last_error", "ik_version", "ik_set_robot", "ik_check_limits", "ik_fk", "ik_fk_chain",
                     "ik_fabrik_solve", "ik_fabrik_solve_fk", "ik_fabrik_calc", "ik_fabrik_reset_order", "ik_ann_load", "ik_ann_solve",
-                    "ik_refine", "ik_ann_solve_refined",
+                    "ik_refine", "ik_ann_solve_refined", "ik_analytic_solve",
                     "ik_stats_fetch", "ik_ctx_set_timing", "ik_kernel_times",
                     "ik_ctx_set_debug", "ik_debug_read", "ik_ann_set_mode", "ik_ann_get_mode",
                     "ik_ann_effective_mode",
@@ -137,6 +138,8 @@ def load_library(path: str = LIB_PATH):
                                 ctypes.c_int, st]
         L.ik_ann_solve_refined.argtypes = [vp, dp, i64, ctypes.c_double, i32, ctypes.c_double, dp,
                                            ip, dp, dp, ctypes.c_int, st]
+        L.ik_analytic_solve.argtypes = [vp, dp, dp, i64, ctypes.c_int, dp, dp, dp, ctypes.c_int,
+                                        st]
         L.ik_stats_fetch.argtypes = [vp, st]
         L.ik_ctx_sync.argtypes = [vp]
         L.ik_comm_set_timeout.argtypes = [vp, ctypes.c_double]
@@ -558,6 +561,40 @@ class Context:
         self._on_torch_stream(lambda: self._check(self.lib.ik_ann_solve_refined(
             self.handle, args[0], n, float(tol), int(max_iter), float(damping), args[1], args[2],
             args[3], args[4], flags, ctypes.byref(s))))
+        return s
+
+    # -- analytic (include/ikhip.h "Analytic") ----------------------------------
+    def analytic_solve(self, pts, pitch=None, elbow=IK_ELBOW_UP, nearest=False,
+                       check_limits=True, want_pitch=True, want_fk_err=True):
+        """Closed-form solve of pts (n x 3) at tool pitch `pitch` (None: every goal's
+        own elevation; a scalar or n values) on the elbow branch -1 / +1, host arrays:
+        returns (angles n x 4 f64, pitch used or None, fk_err or None, stats)."""
+        s = IkStats()
+        p = _host(pts, np.float64, 3)
+        n = p.shape[0]
+        ph = None if pitch is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(pitch, np.float64), (n,)))
+        ang = np.empty((n, 4), np.float64)
+        po = np.empty(n, np.float64) if want_pitch else None
+        err = np.empty(n, np.float64) if want_fk_err else None
+        flags = (0 if check_limits else IK_F_NO_LIMITS) | (IK_F_PITCH_NEAREST if nearest else 0)
+        self._check(self.lib.ik_analytic_solve(self.handle, _ptr(p), _ptr(ph), n, int(elbow),
+                                               _ptr(ang), _ptr(po), _ptr(err), flags,
+                                               ctypes.byref(s)))
+        return ang, po, err, s
+
+    def analytic_solve_device(self, pts, ang, pitch=None, pitch_out=None, fk_err=None,
+                              elbow=IK_ELBOW_UP, flags: int = IK_F_DEVICE):
+        s = IkStats()
+        n = int(pts.shape[0])
+        args = (self._dev(pts, "float64", (n, 3), "pts"),
+                self._dev(pitch, "float64", (n,), "pitch"),
+                self._dev(ang, "float64", (n, 4), "ang"),
+                self._dev(pitch_out, "float64", (n,), "pitch_out"),
+                self._dev(fk_err, "float64", (n,), "fk_err"))
+        self._on_torch_stream(lambda: self._check(self.lib.ik_analytic_solve(
+            self.handle, args[0], args[1], n, int(elbow), args[2], args[3], args[4], flags,
+            ctypes.byref(s))))
         return s
 
     # -- training (include/ikhip.h "ANN training") ---------------------------

@@ -16,6 +16,10 @@ reference's constructor), --device, and for --method ann --refine-tol FLOAT
 [--refine-iter INT, default 20]: the network's angles are polished on the GPU by
 the damped-least-squares refine (kinematics/refine.py) and written as float64;
 --verbose then reports the network's and the polished FK error.
+`--method analytic [--pitch FLOAT] [--elbow up|down] [--nearest-pitch]` (not in the
+reference) solves in closed form at a chosen tool pitch theta2 + theta3 + theta4 and
+elbow branch (kinematics/analytic.py); a fourth CSV column `pitch` gives one pitch per
+point; --verbose then reports the FK round trip and how many pitches were moved.
 `--generate-data --shape {circle,cube,cube_random,random,spring,random_dist}` runs
 the reference's generators (robot/position_generator.py, cli.py:80-229) with the
 same arguments: --to-file writes the x,y,z CSV, --verbose prints the shape's
@@ -32,6 +36,8 @@ import numpy as np
 EXAMPLES = {
     "ann": "--inverse-kine --method ann --model model_filename.h5 --points filename.csv",
     "fabrik": "--inverse-kine --method fabrik --points filename.csv",
+    "analytic": "--inverse-kine --method analytic --points filename.csv --pitch -1.5708 "
+                "--elbow up --nearest-pitch",
     "circle": "--generate-data --shape circle --radius 3 --samples 20 --center 1,5,2",
     "cube": "--generate-data --shape cube --step 0.75 --dim 2,3,4 --start 1,2,3",
     "cube_random": "--generate-data --shape cube_random --step 0.75 --dim 2,3,4 --start 1,2,3",
@@ -52,7 +58,7 @@ def _parser():
     g = p.add_mutually_exclusive_group()
     g.add_argument("--inverse-kine", action="store_true")
     g.add_argument("--generate-data", action="store_true")
-    p.add_argument("--method", choices=["ann", "fabrik"])
+    p.add_argument("--method", choices=["ann", "fabrik", "analytic"])
     p.add_argument("--shape", choices=list(SHAPE_ARGS))
     p.add_argument("--example", action="store_true")
     p.add_argument("--points", type=str, help=".csv file name with stored trajectory points")
@@ -67,6 +73,12 @@ def _parser():
     p.add_argument("--refine-tol", type=float, default=None,
                    help="ANN: polish the angles until |FK(theta) - p| <= this")
     p.add_argument("--refine-iter", type=int, default=20, help="ANN: refine step cap")
+    p.add_argument("--pitch", type=float, default=None,
+                   help="analytic: tool pitch theta2 + theta3 + theta4 of every point (radians)")
+    p.add_argument("--elbow", choices=["up", "down"], default=None,
+                   help="analytic: elbow branch (default up, theta3 <= 0)")
+    p.add_argument("--nearest-pitch", action="store_true",
+                   help="analytic: move an unreachable pitch to the nearest reachable one")
     # data generators
     p.add_argument("--samples", type=int)
     p.add_argument("--dim", type=str)
@@ -83,6 +95,15 @@ def _parser():
 def _read_points(path):
     import pandas as pd
     return pd.read_csv(path).values.tolist()
+
+
+def _read_points_pitch(path):
+    """(points, per-point pitches or None): a fourth column `pitch` is split off."""
+    import pandas as pd
+    df = pd.read_csv(path)
+    if "pitch" not in df.columns:
+        return df.values.tolist(), None
+    return df.drop(columns="pitch").values.tolist(), df["pitch"].to_numpy(np.float64)
 
 
 def _save_angles(data, filename):
@@ -116,16 +137,30 @@ def _ikine(args, parser):
         parser.error("the following arguments are required: --model")
     if args.refine_tol is not None and args.method != "ann":
         parser.error("--refine-tol is only valid with --method ann")
-    from .kinematics.inverse import AnnInverseKinematics, FabrikInverseKinematics
-    points = _read_points(args.points)
+    if args.method != "analytic":
+        for flag, given in (("--pitch", args.pitch is not None), ("--elbow", args.elbow is not None),
+                            ("--nearest-pitch", args.nearest_pitch)):
+            if given:
+                parser.error(f"{flag} is only valid with --method analytic")
+    from .kinematics.inverse import AnalyticInverseKinematics, AnnInverseKinematics, \
+        FabrikInverseKinematics
     dh = [list(r) for r in Robot.dh_matrix]
+    if args.method == "analytic":
+        points, pitches = _read_points_pitch(args.points)
+        if pitches is not None and args.pitch is not None:
+            parser.error("--pitch is not valid with a points file that has a pitch column")
+        ik = AnalyticInverseKinematics(dh, Robot.links_lengths, Robot.effector_workspace_limits,
+                                       pitch=args.pitch if pitches is None else pitches,
+                                       elbow=args.elbow or "up", nearest=args.nearest_pitch)
+    else:
+        points = _read_points(args.points)
     if args.method == "ann":
         refine = (None if args.refine_tol is None
                   else {"tol": args.refine_tol, "max_iter": args.refine_iter})
         ik = AnnInverseKinematics(dh, Robot.links_lengths, Robot.effector_workspace_limits,
                                   refine=refine)
         ik.load_model(args.model)
-    else:
+    elif args.method == "fabrik":
         ik = FabrikInverseKinematics(dh, Robot.links_lengths, Robot.effector_workspace_limits,
                                      args.tol, args.max_iter)
     try:
@@ -141,6 +176,9 @@ def _ikine(args, parser):
                   f"refined to tol {args.refine_tol:g} in max {int(it.max())} steps "
                   f"(mean {it.mean():.3g}), {ik.last_stats.n_capped} of {len(it)} points not "
                   "converged")
+        if args.method == "analytic":
+            print(f"analytic: max |FK(theta) - p| = {np.nanmax(ik.last_fk_err):.6g} (in the solve's "
+                  f"launch), {ik.last_stats.n_capped} of {len(points)} pitches moved")
     if args.to_file is not None:
         _save_angles(joint_angles, args.to_file)
     return 0

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "ik_analytic_plan.h"
 #include "ik_fabrik_prior.h"
 #include "ik_internal.h"
 
@@ -180,6 +181,8 @@ int set_dev(ik_ctx *c) {
 }
 
 int check_flags(const char *who, int flags, const void *ang) {
+  if (flags & IK_F_PITCH_NEAREST)  // (ik_analytic_solve clears it before it comes here)
+    return fail(IK_E_BADARG, std::string(who) + ": IK_F_PITCH_NEAREST is ik_analytic_solve's");
   if ((flags & IK_F_ASYNC) && !(flags & IK_F_DEVICE))
     return fail(IK_E_BADARG, std::string(who) + ": IK_F_ASYNC requires IK_F_DEVICE");
   if ((flags & IK_F_DEVICE) && (reinterpret_cast<uintptr_t>(ang) & 15))
@@ -875,6 +878,40 @@ int ik_ann_solve_refined(ik_ctx *c, const double *pts, int64_t n, double tol, in
   launch_reset_stats(c->d_stats, c->stream);
   launch_refine_f32(c->rconst, dp, dseed, n, tol, max_iter, damping, st.at<double>(r_ang),
                     st.at<int32_t>(r_it), st.at<double>(r_fe), limits, c->d_stats, c->stream);
+  IK_HIP(hipGetLastError());
+  if ((rc = st.flush())) return rc;
+  return finish(c, flags, stats);
+}
+
+// ---- analytic (ik_analytic.hip) ------------------------------------------------
+int ik_analytic_solve(ik_ctx *c, const double *pts, const double *pitch, int64_t n, int elbow,
+                      double *ang, double *pitch_out, double *fk_err, int flags, ik_stats *stats) {
+  if (!c || n < 0 || (n > 0 && (!pts || !ang)))
+    return fail(IK_E_BADARG, "ik_analytic_solve: bad args");
+  if (elbow != IK_ELBOW_UP && elbow != IK_ELBOW_DOWN)
+    return fail(IK_E_BADARG, "ik_analytic_solve: elbow " + std::to_string(elbow) +
+                                 " is neither IK_ELBOW_UP (-1) nor IK_ELBOW_DOWN (1)");
+  const bool nearest = flags & IK_F_PITCH_NEAREST;
+  flags &= ~IK_F_PITCH_NEAREST;  // (the one call that takes the bit)
+  int rc = check_flags("ik_analytic_solve", flags, ang);
+  if (rc) return rc;
+  AnalyticRobot robot;  // (the kernel reads the same lengths from the robot constants)
+  const std::string why = analytic_robot(c->robot.dh, &robot);
+  if (!why.empty())
+    return fail(IK_E_BADARG, "ik_analytic_solve: the robot is not a yaw joint + planar "
+                             "three-link chain: " + why);
+  if ((rc = set_dev(c))) return rc;
+  KtScope kts(c);
+  Stage st(c, flags);
+  const int r_pts = st.in(pts, (size_t)n * 24), r_ph = pitch ? st.in(pitch, (size_t)n * 8) : -1,
+            r_ang = st.out(ang, (size_t)n * 32), r_po = st.out(pitch_out, (size_t)n * 8),
+            r_fe = st.out(fk_err, (size_t)n * 8);
+  if ((rc = st.reserve())) return rc;
+  launch_reset_stats(c->d_stats, c->stream);
+  launch_analytic(c->rconst, st.at<const double>(r_pts),
+                  r_ph < 0 ? nullptr : st.at<const double>(r_ph), n, elbow, nearest,
+                  st.at<double>(r_ang), st.at<double>(r_po), st.at<double>(r_fe),
+                  !(flags & IK_F_NO_LIMITS), c->d_stats, c->stream);
   IK_HIP(hipGetLastError());
   if ((rc = st.flush())) return rc;
   return finish(c, flags, stats);

@@ -6,7 +6,9 @@ one call instead of a Python loop over points:
 
 * FabrikInverseKinematics.ikine -> libikhip ik_fabrik_solve (float64, iteration
   counts bit-exact with the reference);
-* AnnInverseKinematics.ikine    -> libikhip ik_ann_solve (fused fp32 MLP).
+* AnnInverseKinematics.ikine    -> libikhip ik_ann_solve (fused fp32 MLP);
+* AnalyticInverseKinematics.ikine (not in the reference) -> libikhip
+  ik_analytic_solve (closed form with a chosen tool pitch and elbow branch).
 
 Errors follow the reference's sequential semantics: the workspace check covers
 every point first (inverse.py:117,153) and raises OutOfRobotReachException for
@@ -23,6 +25,7 @@ import numpy as np
 
 from .. import _native
 from ..robot.robot import OutOfRobotReachException
+from .analytic import ELBOWS
 from .ann import ANN, as_features as as_ann_points
 from .forward import ForwardKinematics
 from .fabrik import Fabrik
@@ -173,4 +176,45 @@ class AnnInverseKinematics(InverseKinematics):
         self.last_stats = st
         if st.first_oob >= 0:
             self._raise_out_of_reach(dest_points, st.first_oob)
+        return ang.tolist()
+
+
+class AnalyticInverseKinematics(InverseKinematics):
+    """Closed-form inverse kinematics with a chosen tool pitch (theta2 + theta3 +
+    theta4) and elbow branch, for a robot that is a yaw joint followed by a planar
+    three-link chain (libikhip ik_analytic_solve, kinematics/analytic.py).  Not in the
+    reference.  pitch: None (the tool points away from the shoulder), a scalar or one
+    value per point; elbow "up" (theta3 <= 0) or "down"; nearest: a pitch at which
+    the goal cannot be reached moves to the nearest one at which it can."""
+
+    def __init__(self, dh_matrix, joints_distances, workspace_limits, pitch=None, elbow="up",
+                 nearest=False):
+        super().__init__(dh_matrix, joints_distances, workspace_limits)
+        if elbow not in ELBOWS:
+            raise ValueError(f"elbow: {elbow!r} is neither 'up' nor 'down'")
+        self.pitch = pitch
+        self.elbow = elbow
+        self.nearest = bool(nearest)
+        self.last_pitch = None
+        self.last_fk_err = None
+
+    def ikine(self, dest_points, pitch=None):
+        """Joint angles [theta1..theta4] (float64) for every destination point; a
+        pitch given here overrides the constructor's."""
+        pts = as_points(dest_points)
+        if pts.shape[0] == 0:
+            return []
+        want = self.pitch if pitch is None else pitch
+        ang, used, err, st = self._ctx().analytic_solve(pts, want, ELBOWS[self.elbow],
+                                                        self.nearest)
+        self.last_stats, self.last_pitch, self.last_fk_err = st, used, err
+        if st.first_oob >= 0:
+            self._raise_out_of_reach(dest_points, st.first_oob)
+        if st.first_err >= 0:
+            i = st.first_err
+            asked = 'None' if want is None else np.broadcast_to(
+                np.asarray(want, np.float64), (pts.shape[0],))[i]
+            raise OutOfRobotReachException(
+                f'Inverse Kinematics exception, point {dest_points[i]} cannot be reached '
+                f'with tool pitch {asked}')
         return ang.tolist()
