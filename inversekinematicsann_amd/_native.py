@@ -422,8 +422,10 @@ class Context:
                                             0, ctypes.byref(s)))
         return out, it, s
 
-    def ann_load(self, weights: Sequence, biases: Sequence, acts: Sequence[str], x_mean,
-                 x_scale, y_mean, y_scale):
+    @staticmethod
+    def _dense_stack(weights, biases, acts):
+        """A Dense stack as the ABI takes it: (dims, (n_layers, dims*, acts*, W**, b**),
+        the arrays those pointers need alive)."""
         Ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
         bs = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in biases]
         nl = len(Ws)
@@ -435,9 +437,13 @@ class Context:
         acts_a = np.array([ACTS[a] for a in acts], np.int32)
         wp = (ctypes.c_void_p * nl)(*[w.ctypes.data for w in Ws])
         bp = (ctypes.c_void_p * nl)(*[b.ctypes.data for b in bs])
+        return dims, (nl, _ptr(dims_a), _ptr(acts_a), wp, bp), (Ws, bs, dims_a, acts_a)
+
+    def ann_load(self, weights: Sequence, biases: Sequence, acts: Sequence[str], x_mean,
+                 x_scale, y_mean, y_scale):
+        _, stack, _alive = self._dense_stack(weights, biases, acts)
         sc = [_host(v, np.float64).reshape(-1) for v in (x_mean, x_scale, y_mean, y_scale)]
-        self._check(self.lib.ik_ann_load(self.handle, nl, _ptr(dims_a), _ptr(acts_a), wp, bp,
-                                         *[_ptr(v) for v in sc]))
+        self._check(self.lib.ik_ann_load(self.handle, *stack, *[_ptr(v) for v in sc]))
         self._warn_mode()
 
     def ann_set_mode(self, mode: str):
@@ -602,20 +608,9 @@ class Context:
                     max_batch: int = 32, lr: float = 1e-5, beta1: float = 0.9,
                     beta2: float = 0.999, eps: float = 1e-7):
         """ik_ann_train_begin: upload the initial weights; Keras' Adam defaults."""
-        Ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
-        bs = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in biases]
-        nl = len(Ws)
-        dims = [Ws[0].shape[0]] + [w.shape[1] for w in Ws]
-        for l in range(nl):
-            if Ws[l].shape != (dims[l], dims[l + 1]) or bs[l].shape != (dims[l + 1],):
-                raise ValueError(f"layer {l}: kernel {Ws[l].shape} / bias {bs[l].shape} mismatch")
-        dims_a = np.array(dims, np.int32)
-        acts_a = np.array([ACTS[a] for a in acts], np.int32)
-        wp = (ctypes.c_void_p * nl)(*[w.ctypes.data for w in Ws])
-        bp = (ctypes.c_void_p * nl)(*[b.ctypes.data for b in bs])
-        self._check(self.lib.ik_ann_train_begin(self.handle, nl, _ptr(dims_a), _ptr(acts_a), wp,
-                                                bp, int(max_batch), float(lr), float(beta1),
-                                                float(beta2), float(eps)))
+        dims, stack, _alive = self._dense_stack(weights, biases, acts)
+        self._check(self.lib.ik_ann_train_begin(self.handle, *stack, int(max_batch), float(lr),
+                                                float(beta1), float(beta2), float(eps)))
         self._train_dims = dims
 
     def _train_xy(self, x, y):

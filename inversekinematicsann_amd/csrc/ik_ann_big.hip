@@ -25,6 +25,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "ik_act.h"
 #include "ik_common.h"
 
 namespace ikhip {
@@ -40,22 +41,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kBM = 128;      // chunk granularity of the activation buffers (rows)
 constexpr int kBK = 32;       // K per LDS stage (4 groups of 8)
 constexpr int kLdA = kBK + 4; // LDS row stride in floats (= 4 mod 32: conflict-free b128 reads)
-
-// The fused kernel's activations (ik_ann.hip act_apply): same forms, same bits.
-__device__ __forceinline__ float act_apply(int act, float v) {
-  switch (act) {
-    case IK_ACT_TANH: {
-      const float e = __builtin_amdgcn_exp2f(2.885390081777927f * v);
-      return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + e), 1.0f);
-    }
-    case IK_ACT_RELU:
-      return fmaxf(v, 0.0f);
-    case IK_ACT_SIGMOID:
-      return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
-    default:
-      return v;
-  }
-}
 
 // Input rows: x = f32((p - x_mean) / x_scale) in columns 0..2 of an 8-float row
 // (columns 3..7 zero: the first layer's packed weights are zero there too).

@@ -29,6 +29,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "ik_act.h"
 #include "ik_common.h"
 
 namespace ikhip {
@@ -105,32 +106,10 @@ __device__ __forceinline__ void stamp(unsigned long long *p) {
 #endif
 }
 
-// Activations with the hardware exp2 / reciprocal (1 ulp each).  tanh is
-// 1 - 2 / (1 + e), e = exp2(2 log2(e) v): one exp, one add, one reciprocal and one
-// fma per element, absolute error <= ~2.5e-7 (tests/test_gpu_parity.py
-// ::test_ann_tanh_accuracy); the limits come out exactly (e = inf -> 1, e = 0 ->
-// -1) and NaN propagates.  The r02 form sign(v) (1 - e') / (1 + e'), e' =
-// exp2(-2 log2(e) |v|), needs a subtraction, a multiply and a sign copy more:
-// tools/ubench.hip `act` measured 39.0 -> 35.5 cycles per element slot (-9 %), and
-// exp2 from a degree-6 polynomial on the full-rate pipe (v_pk_fma_f32) instead of
-// v_exp_f32 58.5 (+50 %: v_exp_f32 issues in 8 cycles, the polynomial's range
-// reduction, six packed fmas and exponent insert in more) -- profiles/r03/ubench.
-template <int ACT>
-__device__ __forceinline__ float act_apply(float v) {
-  if constexpr (ACT == IK_ACT_TANH) {
-    const float e = __builtin_amdgcn_exp2f(2.885390081777927f * v);
-    return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + e), 1.0f);
-  } else if constexpr (ACT == IK_ACT_RELU) {
-    return fmaxf(v, 0.0f);
-  } else if constexpr (ACT == IK_ACT_SIGMOID) {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
-  } else {
-    return v;
-  }
-}
-
 // Two elements at once: the adds / multiplies / fmas become packed-fp32
-// instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32).
+// instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32).  The packed forms
+// here are this kernel's own; element for element they compute ik_act.h's scalar
+// act_apply<ACT>, which they must keep matching bit for bit.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int ACT>
 __device__ __forceinline__ f32x2 act_apply2(f32x2 v) {

@@ -13,7 +13,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -33,8 +32,6 @@ const double kDefaultLinks[4] = {2.0, 2.0, 2.0, 2.0};
 const double kDefaultLimits[6] = {0.0, 6.0, -6.0, 6.0, -3.0, 6.0};
 
 thread_local KTimer *g_kt = nullptr;
-
-void train_release(ik_ctx *c);  // (below, with the training calls)
 
 static_assert(sizeof(FabPrior::key) == sizeof(FabOrderDev::key), "prior = one cost table");
 
@@ -915,328 +912,6 @@ int ik_analytic_solve(ik_ctx *c, const double *pts, const double *pitch, int64_t
   IK_HIP(hipGetLastError());
   if ((rc = st.flush())) return rc;
   return finish(c, flags, stats);
-}
-
-}  // extern "C"
-
-// ---- training (ik_train.hip) -------------------------------------------------
-namespace {
-
-void train_free_data(TrainDev *T) {
-  if (T->data_block) (void)hipFree(T->data_block);
-  T->data_block = nullptr;
-  T->X = T->Y = T->Xs = T->Ys = T->Xv = T->Yv = nullptr;
-  T->perm = nullptr;
-  T->n_train = T->n_val = 0;
-}
-
-void train_release(ik_ctx *c) {
-  TrainDev *T = c->train;
-  if (!T) return;
-  (void)hipStreamSynchronize(c->stream);
-  train_free_data(T);
-  if (T->loss) (void)hipFree(T->loss);
-  if (T->block) (void)hipFree(T->block);
-  delete T;
-  c->train = nullptr;
-}
-
-// Keras Adam's step size at step t (1-based), float64 on the host
-AdamDev train_adam(const TrainDev *T, int64_t t) {
-  const double a = T->lr * std::sqrt(1.0 - std::pow(T->beta2, (double)t)) /
-                   (1.0 - std::pow(T->beta1, (double)t));
-  AdamDev ad;
-  ad.b1 = T->beta1;
-  ad.omb1 = 1.0 - T->beta1;
-  ad.b2 = T->beta2;
-  ad.omb2 = 1.0 - T->beta2;
-  ad.eps = (float)T->eps;
-  ad.alpha = (float)a;
-  return ad;
-}
-
-int train_slots(ik_ctx *c, int64_t want) {
-  TrainDev *T = c->train;
-  if (want <= T->loss_slots) return IK_OK;
-  IK_HIP(hipStreamSynchronize(c->stream));
-  if (T->loss) IK_HIP(hipFree(T->loss));
-  T->loss = nullptr;
-  T->loss_slots = 0;
-  IK_HIP(hipMalloc(reinterpret_cast<void **>(&T->loss), (size_t)want * sizeof(double)));
-  T->loss_slots = want;
-  return IK_OK;
-}
-
-// One batch from host rows: forward, loss, backward (Adam update or gradients out).
-int train_batch(ik_ctx *c, const char *who, const float *x, const float *y, int rows, bool adam,
-                double *loss) {
-  TrainDev *T = c->train;
-  if (!T) return fail(IK_E_BADARG, std::string(who) + ": before ik_ann_train_begin");
-  if (!x || !y || rows < 1)
-    return fail(IK_E_BADARG, std::string(who) + ": NULL rows or rows < 1");
-  if (rows > T->max_batch)
-    return fail(IK_E_BADARG, std::string(who) + ": " + std::to_string(rows) +
-                                 " rows exceed max_batch " + std::to_string(T->max_batch));
-  const int d0 = T->dims[0], dL = T->dims[T->n_layers];
-  IK_HIP(hipMemcpyAsync(T->A[0], x, (size_t)rows * d0 * sizeof(float), hipMemcpyHostToDevice,
-                        c->stream));
-  IK_HIP(hipMemcpyAsync(T->y, y, (size_t)rows * dL * sizeof(float), hipMemcpyHostToDevice,
-                        c->stream));
-  train_forward(*T, T->A[0], rows, c->stream);
-  train_loss(*T, T->y, rows, T->loss, true, c->stream);
-  train_backward(*T, T->A[0], rows, adam, train_adam(T, T->t + 1), c->stream);
-  IK_HIP(hipGetLastError());
-  double sum = 0.0;
-  IK_HIP(hipMemcpyAsync(&sum, T->loss, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  IK_HIP(hipStreamSynchronize(c->stream));
-  if (adam) T->t += 1;
-  if (loss) *loss = sum / ((double)rows * (double)dL);
-  return IK_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ik_ann_train_begin(ik_ctx *c, int n_layers, const int32_t *dims, const int32_t *acts,
-                       const float *const *W, const float *const *b, int max_batch, double lr,
-                       double beta1, double beta2, double eps) {
-  if (!c || !dims || !acts || !W || !b)
-    return fail(IK_E_BADARG, "ik_ann_train_begin: NULL argument");
-  if (n_layers < 1 || n_layers > kTrainMaxLayers)
-    return fail(IK_E_BADARG, "ik_ann_train_begin: n_layers must be 1.." +
-                                 std::to_string(kTrainMaxLayers));
-  for (int l = 0; l <= n_layers; ++l)
-    if (dims[l] < 1 || dims[l] > kTrainMaxWidth)
-      return fail(IK_E_BADARG, "ik_ann_train_begin: dims[" + std::to_string(l) + "] must be 1.." +
-                                   std::to_string(kTrainMaxWidth));
-  for (int l = 0; l < n_layers; ++l) {
-    if (acts[l] < IK_ACT_LINEAR || acts[l] > IK_ACT_SIGMOID)
-      return fail(IK_E_BADARG, "ik_ann_train_begin: unknown activation");
-    if (!W[l] || !b[l]) return fail(IK_E_BADARG, "ik_ann_train_begin: NULL layer weights");
-  }
-  if (max_batch < 1 || max_batch > kTrainMaxBatch)
-    return fail(IK_E_BADARG, "ik_ann_train_begin: max_batch must be 1.." +
-                                 std::to_string(kTrainMaxBatch));
-  if (!(lr > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) ||
-      !(eps >= 0.0) || !std::isfinite(lr) || !std::isfinite(eps))
-    return fail(IK_E_BADARG, "ik_ann_train_begin: bad Adam parameters");
-  int rc = set_dev(c);
-  if (rc) return rc;
-  train_release(c);  // a second begin starts over
-  TrainDev *T = new (std::nothrow) TrainDev;
-  if (!T) return fail(IK_E_HIP, "ik_ann_train_begin: out of host memory");
-  c->train = T;
-  T->n_layers = n_layers;
-  T->max_batch = max_batch;
-  T->lr = lr, T->beta1 = beta1, T->beta2 = beta2, T->eps = eps;
-  int widest = 1;
-  for (int l = 0; l <= n_layers; ++l) {
-    T->dims[l] = dims[l];
-    widest = dims[l] > widest ? dims[l] : widest;
-  }
-  for (int l = 0; l < n_layers; ++l) T->act[l] = acts[l];
-  // one block, every part a multiple of 64 floats
-  std::vector<std::pair<float **, size_t>> parts;
-  auto want = [&](float **p, size_t n) { parts.push_back({p, (n + 63) / 64 * 64}); };
-  for (int l = 0; l < n_layers; ++l) {
-    const size_t kn = (size_t)dims[l] * dims[l + 1], n = (size_t)dims[l + 1];
-    want(&T->W[l], kn), want(&T->mW[l], kn), want(&T->vW[l], kn), want(&T->gW[l], kn);
-    want(&T->b[l], n), want(&T->mb[l], n), want(&T->vb[l], n), want(&T->gb[l], n);
-  }
-  for (int l = 0; l <= n_layers; ++l) want(&T->A[l], (size_t)max_batch * dims[l]);
-  want(&T->y, (size_t)max_batch * dims[n_layers]);
-  want(&T->dZ[0], (size_t)max_batch * widest), want(&T->dZ[1], (size_t)max_batch * widest);
-  size_t total = 0;
-  for (auto &p : parts) total += p.second;
-  auto bail = [&](int code) {
-    train_release(c);
-    return code;
-  };
-  if (hipMalloc(&T->block, total * sizeof(float)) != hipSuccess) {
-    T->block = nullptr;
-    (void)hipGetLastError();
-    return bail(fail(IK_E_HIP, "ik_ann_train_begin: hipMalloc of the training state failed"));
-  }
-  size_t off = 0;
-  for (auto &p : parts) {
-    *p.first = static_cast<float *>(T->block) + off;
-    off += p.second;
-  }
-  if ((rc = train_slots(c, 1))) return bail(rc);
-  hipError_t e = hipMemsetAsync(T->block, 0, total * sizeof(float), c->stream);
-  for (int l = 0; l < n_layers && e == hipSuccess; ++l) {
-    e = hipMemcpyAsync(T->W[l], W[l], (size_t)dims[l] * dims[l + 1] * sizeof(float),
-                       hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(T->b[l], b[l], (size_t)dims[l + 1] * sizeof(float),
-                         hipMemcpyHostToDevice, c->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess)
-    return bail(fail(IK_E_HIP, std::string("ik_ann_train_begin: ") + hipGetErrorString(e)));
-  return IK_OK;
-}
-
-int ik_ann_train_data(ik_ctx *c, const float *x, const float *y, int64_t n_train, const float *xv,
-                      const float *yv, int64_t n_val) {
-  if (!c) return fail(IK_E_BADARG, "ik_ann_train_data: NULL context");
-  TrainDev *T = c->train;
-  if (!T) return fail(IK_E_BADARG, "ik_ann_train_data: before ik_ann_train_begin");
-  if (!x || !y || n_train < 1 || n_train > INT32_MAX || n_val < 0 || n_val > INT32_MAX ||
-      (n_val > 0 && (!xv || !yv)))
-    return fail(IK_E_BADARG, "ik_ann_train_data: bad args");
-  int rc = set_dev(c);
-  if (rc) return rc;
-  IK_HIP(hipStreamSynchronize(c->stream));
-  train_free_data(T);
-  const size_t d0 = (size_t)T->dims[0], dL = (size_t)T->dims[T->n_layers];
-  auto up = [](size_t n) { return (n + 63) / 64 * 64; };
-  const size_t fx = up((size_t)n_train * d0), fy = up((size_t)n_train * dL),
-               fxv = up((size_t)n_val * d0), fyv = up((size_t)n_val * dL),
-               fp = up((size_t)n_train);
-  IK_HIP(hipMalloc(&T->data_block, (2 * fx + 2 * fy + fxv + fyv + fp) * sizeof(float)));
-  float *p = static_cast<float *>(T->data_block);
-  T->X = p, p += fx;
-  T->Xs = p, p += fx;
-  T->Y = p, p += fy;
-  T->Ys = p, p += fy;
-  T->Xv = p, p += fxv;
-  T->Yv = p, p += fyv;
-  T->perm = reinterpret_cast<int32_t *>(p);
-  T->n_train = n_train;
-  T->n_val = n_val;
-  IK_HIP(hipMemcpyAsync(T->X, x, (size_t)n_train * d0 * 4, hipMemcpyHostToDevice, c->stream));
-  IK_HIP(hipMemcpyAsync(T->Y, y, (size_t)n_train * dL * 4, hipMemcpyHostToDevice, c->stream));
-  if (n_val > 0) {
-    IK_HIP(hipMemcpyAsync(T->Xv, xv, (size_t)n_val * d0 * 4, hipMemcpyHostToDevice, c->stream));
-    IK_HIP(hipMemcpyAsync(T->Yv, yv, (size_t)n_val * dL * 4, hipMemcpyHostToDevice, c->stream));
-  }
-  IK_HIP(hipStreamSynchronize(c->stream));
-  return IK_OK;
-}
-
-int ik_ann_train_grads(ik_ctx *c, const float *x, const float *y, int rows, float *const *dW,
-                       float *const *db, double *loss) {
-  if (!c) return fail(IK_E_BADARG, "ik_ann_train_grads: NULL context");
-  if (c->train && (!dW || !db)) return fail(IK_E_BADARG, "ik_ann_train_grads: NULL outputs");
-  int rc = set_dev(c);
-  if (rc) return rc;
-  KtScope kts(c);
-  if ((rc = train_batch(c, "ik_ann_train_grads", x, y, rows, false, loss))) return rc;
-  const TrainDev *T = c->train;
-  for (int l = 0; l < T->n_layers; ++l) {
-    if (dW[l])
-      IK_HIP(hipMemcpyAsync(dW[l], T->gW[l], (size_t)T->dims[l] * T->dims[l + 1] * 4,
-                            hipMemcpyDeviceToHost, c->stream));
-    if (db[l])
-      IK_HIP(hipMemcpyAsync(db[l], T->gb[l], (size_t)T->dims[l + 1] * 4, hipMemcpyDeviceToHost,
-                            c->stream));
-  }
-  IK_HIP(hipStreamSynchronize(c->stream));
-  return IK_OK;
-}
-
-int ik_ann_train_step(ik_ctx *c, const float *x, const float *y, int rows, double *loss) {
-  if (!c) return fail(IK_E_BADARG, "ik_ann_train_step: NULL context");
-  int rc = set_dev(c);
-  if (rc) return rc;
-  KtScope kts(c);
-  return train_batch(c, "ik_ann_train_step", x, y, rows, true, loss);
-}
-
-int ik_ann_train_epoch(ik_ctx *c, const int32_t *perm, int batch, double *train_loss_out,
-                       double *val_loss_out) {
-  if (!c) return fail(IK_E_BADARG, "ik_ann_train_epoch: NULL context");
-  TrainDev *T = c->train;
-  if (!T) return fail(IK_E_BADARG, "ik_ann_train_epoch: before ik_ann_train_begin");
-  if (!T->data_block) return fail(IK_E_BADARG, "ik_ann_train_epoch: before ik_ann_train_data");
-  if (batch < 1 || batch > T->max_batch)
-    return fail(IK_E_BADARG, "ik_ann_train_epoch: batch " + std::to_string(batch) +
-                                 " outside 1..max_batch " + std::to_string(T->max_batch));
-  if (perm)
-    for (int64_t i = 0; i < T->n_train; ++i)
-      if (perm[i] < 0 || perm[i] >= T->n_train)
-        return fail(IK_E_BADARG, "ik_ann_train_epoch: perm[" + std::to_string(i) + "] = " +
-                                     std::to_string(perm[i]) + " outside 0.." +
-                                     std::to_string(T->n_train - 1));
-  int rc = set_dev(c);
-  if (rc) return rc;
-  const int64_t steps = (T->n_train + batch - 1) / batch;
-  const int64_t vchunks = (T->n_val + T->max_batch - 1) / T->max_batch;
-  if ((rc = train_slots(c, steps + vchunks))) return rc;
-  KtScope kts(c);
-  const size_t d0 = (size_t)T->dims[0], dL = (size_t)T->dims[T->n_layers];
-  const float *xs = T->X, *ys = T->Y;
-  if (perm) {
-    IK_HIP(hipMemcpyAsync(T->perm, perm, (size_t)T->n_train * sizeof(int32_t),
-                          hipMemcpyHostToDevice, c->stream));
-    train_gather(*T, c->stream);
-    xs = T->Xs, ys = T->Ys;
-  }
-  for (int64_t s = 0; s < steps; ++s) {
-    const int64_t r0 = s * batch;
-    const int rows = (int)(T->n_train - r0 < batch ? T->n_train - r0 : batch);
-    train_forward(*T, xs + r0 * d0, rows, c->stream);
-    train_loss(*T, ys + r0 * dL, rows, T->loss + s, true, c->stream);
-    train_backward(*T, xs + r0 * d0, rows, true, train_adam(T, T->t + 1), c->stream);
-    T->t += 1;
-  }
-  // the end-of-epoch weights over the validation rows, forward only
-  for (int64_t v = 0; v < vchunks; ++v) {
-    const int64_t r0 = v * T->max_batch;
-    const int rows = (int)(T->n_val - r0 < T->max_batch ? T->n_val - r0 : T->max_batch);
-    train_forward(*T, T->Xv + r0 * d0, rows, c->stream);
-    train_loss(*T, T->Yv + r0 * dL, rows, T->loss + steps + v, false, c->stream);
-  }
-  IK_HIP(hipGetLastError());
-  std::vector<double> sums((size_t)(steps + vchunks));
-  IK_HIP(hipMemcpyAsync(sums.data(), T->loss, sums.size() * sizeof(double), hipMemcpyDeviceToHost,
-                        c->stream));
-  IK_HIP(hipStreamSynchronize(c->stream));
-  // Keras' running mean: the steps' losses weighted by their rows
-  double acc = 0.0;
-  for (int64_t s = 0; s < steps; ++s) {
-    const int64_t r0 = s * batch;
-    const double rows = (double)(T->n_train - r0 < batch ? T->n_train - r0 : batch);
-    acc += sums[(size_t)s] / (rows * (double)dL) * rows;
-  }
-  if (train_loss_out) *train_loss_out = acc / (double)T->n_train;
-  double vs = 0.0;
-  for (int64_t v = 0; v < vchunks; ++v) vs += sums[(size_t)(steps + v)];
-  if (val_loss_out)
-    *val_loss_out = T->n_val > 0 ? vs / ((double)T->n_val * (double)dL) : std::nan("");
-  return IK_OK;
-}
-
-int ik_ann_train_get(ik_ctx *c, int what, float *const *W, float *const *b) {
-  if (!c) return fail(IK_E_BADARG, "ik_ann_train_get: NULL context");
-  const TrainDev *T = c->train;
-  if (!T) return fail(IK_E_BADARG, "ik_ann_train_get: before ik_ann_train_begin");
-  if (what < 0 || what > 2 || !W || !b) return fail(IK_E_BADARG, "ik_ann_train_get: bad args");
-  int rc = set_dev(c);
-  if (rc) return rc;
-  float *const *sw = what == 0 ? T->W : what == 1 ? T->mW : T->vW;
-  float *const *sb = what == 0 ? T->b : what == 1 ? T->mb : T->vb;
-  for (int l = 0; l < T->n_layers; ++l) {
-    if (W[l])
-      IK_HIP(hipMemcpyAsync(W[l], sw[l], (size_t)T->dims[l] * T->dims[l + 1] * 4,
-                            hipMemcpyDeviceToHost, c->stream));
-    if (b[l])
-      IK_HIP(hipMemcpyAsync(b[l], sb[l], (size_t)T->dims[l + 1] * 4, hipMemcpyDeviceToHost,
-                            c->stream));
-  }
-  IK_HIP(hipStreamSynchronize(c->stream));
-  return IK_OK;
-}
-
-int ik_ann_train_end(ik_ctx *c) {
-  if (!c) return fail(IK_E_BADARG, "ik_ann_train_end: NULL context");
-  if (!c->train) return fail(IK_E_BADARG, "ik_ann_train_end: before ik_ann_train_begin");
-  int rc = set_dev(c);
-  if (rc) return rc;
-  train_release(c);
-  return IK_OK;
 }
 
 }  // extern "C"

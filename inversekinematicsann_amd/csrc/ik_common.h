@@ -18,6 +18,7 @@
 
 #include "../../include/ikhip.h"
 #include "ik_ann_pack.h"
+#include "ik_train_plan.h"
 
 namespace ikhip {
 
@@ -649,10 +650,8 @@ void launch_ann_big(const AnnBigModel &m, const RobotDev &r, const double *pts, 
 // weight-gradient GEMM (the bias gradient its last row) with the Adam update in its
 // epilogue.
 // Master weights, moments and gradients are fp32 row-major [in][out] (the Keras
-// kernel layout), unpadded; every activation row is dims[l] floats.
-constexpr int kTrainMaxLayers = 24;
-constexpr int kTrainMaxWidth = 1024;
-constexpr int kTrainMaxBatch = 4096;
+// kernel layout), unpadded; every activation row is dims[l] floats.  The caps,
+// AdamDev and the blocks' layouts: ik_train_plan.h.
 struct TrainDev {
   int n_layers = 0, max_batch = 0;
   int dims[kTrainMaxLayers + 1] = {};
@@ -674,10 +673,6 @@ struct TrainDev {
   int32_t *perm = nullptr;
   int64_t n_train = 0, n_val = 0;
   void *data_block = nullptr;
-};
-struct AdamDev {
-  double b1, omb1, b2, omb2;  // beta, 1 - beta
-  float eps, alpha;           // epsilon, alpha_t
 };
 // A_l = act(A_{l-1} W_l + b_l) for every layer; x: rows x dims[0] device floats.
 void train_forward(const TrainDev &T, const float *x, int rows, hipStream_t st);

@@ -1,8 +1,10 @@
 // ik_internal.h -- the context behind the C ABI and the helpers its
 // translation units share (ik_api.cpp: single-device calls; ik_pipe.cpp: the
-// chunked host-pointer pipeline; ik_shard.hip: the RCCL-sharded calls, whose
-// plan / tail / histogram arithmetic is the host-only ik_shard_plan.cpp).  Not
-// installed; include/ikhip.h is the interface.
+// chunked host-pointer pipeline; ik_train_api.cpp: the training calls, whose
+// layouts / epoch plan / refusals are the host-only ik_train_plan.cpp;
+// ik_shard.hip: the RCCL-sharded calls, whose plan / tail / histogram arithmetic
+// is the host-only ik_shard_plan.cpp).  Not installed; include/ikhip.h is the
+// interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -238,6 +240,8 @@ int fabrik_host_pipeline(ik_ctx *c, const double *pts, int64_t n, double tol, in
                          double *ang, int32_t *iters, double *joints, double *fk_err, int flags,
                          ik_stats *stats);
 void pipe_release(ik_ctx *c);
+// Frees the context's training state, if any (ik_train_api.cpp).
+void train_release(ik_ctx *c);
 // The batch stats of the last sharded call, from the gathered tails (waits).
 int sharded_stats(ik_ctx *c, ik_stats *stats);
 // Releases the communicator; false when aborted work has not drained (its

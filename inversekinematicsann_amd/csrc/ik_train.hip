@@ -28,43 +28,13 @@
 // loaded into registers while the current one's MFMAs run.
 #include <cstdint>
 
+#include "ik_act.h"
 #include "ik_common.h"
 
 namespace ikhip {
 namespace train {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// The inference kernels' activations (ik_ann.hip / ik_ann_big.hip act_apply): same
-// forms, same bits, so a trained model predicts what it was trained to.
-__device__ __forceinline__ float act_apply(int act, float v) {
-  switch (act) {
-    case IK_ACT_TANH: {
-      const float e = __builtin_amdgcn_exp2f(2.885390081777927f * v);
-      return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + e), 1.0f);
-    }
-    case IK_ACT_RELU:
-      return fmaxf(v, 0.0f);
-    case IK_ACT_SIGMOID:
-      return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
-    default:
-      return v;
-  }
-}
-
-// act' from the layer's stored output a = act(z)
-__device__ __forceinline__ float act_deriv(int act, float a) {
-  switch (act) {
-    case IK_ACT_TANH:
-      return 1.0f - a * a;
-    case IK_ACT_RELU:
-      return a > 0.0f ? 1.0f : 0.0f;
-    case IK_ACT_SIGMOID:
-      return a * (1.0f - a);
-    default:
-      return 1.0f;
-  }
-}
 
 // Keras Adam (epsilon outside the square root, the bias corrections folded into
 // alpha_t on the host).  The moments are stored fp32 but each is evaluated in

@@ -260,6 +260,51 @@ def test_training_is_deterministic(traj_data, traj_gpu):
         assert np.array_equal(a, r)
 
 
+def test_epoch_losses_with_ragged_steps_and_validation_chunks():
+    """13 training rows in batches of 5 (steps of 5, 5, 3 rows) and 19 validation
+    rows through max_batch 8 (chunks of 8, 8, 3): both losses of two epochs
+    against the float64 trainer, and the same bits from a second run."""
+    from inversekinematicsann_amd import _native
+    torch = _torch()
+    dims, max_batch, batch, n_train, n_val = (3, 8, 4), 8, 5, 13, 19
+    m = _model(dims, seed=7)
+    x, y = _batch(dims, n_train, seed=8)
+    xv, yv = _batch(dims, n_val, seed=9)
+    rng = np.random.default_rng(1)
+    perms = [rng.permutation(n_train).astype(np.int32) for _ in range(2)]
+
+    def run():
+        c = _native.Context(0)
+        try:
+            c.train_begin(m.weights, m.biases, m.activations, max_batch=max_batch, lr=1e-3)
+            c.train_data(x, y, xv, yv)
+            losses = [c.train_epoch(p, batch) for p in perms]
+            W, b = c.train_get("weights")
+            c.train_end()
+        finally:
+            c.close()
+        return losses, W + b
+
+    losses, params = run()
+    tr = CpuTrainer(m.weights, m.biases, m.activations, torch.float64, lr=1e-3)
+    xv64, yv64 = torch.tensor(xv, dtype=torch.float64), torch.tensor(yv, dtype=torch.float64)
+    for e, p in enumerate(perms):
+        tl = tr.epoch(x, y, p, batch)
+        h = xv64
+        for W, b, a in zip(tr.W, tr.b, tr.acts):  # the end-of-epoch weights
+            h = _act(torch, a, h @ W + b)
+        vl = float(((h - yv64) ** 2).sum()) / (n_val * dims[-1])
+        print(f"epoch {e + 1}: loss {losses[e][0]:.9g} vs {tl:.9g} "
+              f"(rel {abs(losses[e][0] - tl) / tl:.2e}), val {losses[e][1]:.9g} vs {vl:.9g} "
+              f"(rel {abs(losses[e][1] - vl) / vl:.2e})")
+        assert abs(losses[e][0] - tl) <= 1e-5 * abs(tl)
+        assert abs(losses[e][1] - vl) <= 1e-5 * abs(vl)
+    again, params2 = run()
+    assert again == losses
+    for a, r in zip(params2, params):
+        assert np.array_equal(a, r)
+
+
 # ---- 5. end to end -------------------------------------------------------------
 def test_fit_end_to_end(traj_data, tmp_path):
     from inversekinematicsann_amd import _native
