@@ -27,7 +27,7 @@ __device__ __forceinline__ float act_apply(float v) {
     const float e = __builtin_amdgcn_exp2f(2.885390081777927f * v);
     return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + e), 1.0f);
   } else if constexpr (ACT == IK_ACT_RELU) {
-    return fmaxf(v, 0.0f);
+    return v < 0.0f ? 0.0f : v;  // (fmaxf would turn NaN into 0)
   } else if constexpr (ACT == IK_ACT_SIGMOID) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
   } else {

@@ -48,15 +48,17 @@ __global__ __launch_bounds__(256) void annb_in_kernel(const double *__restrict__
                                                       int64_t rows, double xm0, double xm1,
                                                       double xm2, double xs0, double xs1,
                                                       double xs2, RobotDev r, int check_limits,
-                                                      float *__restrict__ X, DevStats *S) {
+                                                      int bounded, float *__restrict__ X,
+                                                      DevStats *S) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows) return;
   const int64_t pt = p0 + i;
   const double px = pts[3 * pt], py = pts[3 * pt + 1], pz = pts[3 * pt + 2];
   if (check_limits && outside(r.lim, px, py, pz)) atomicMin(&S->first_oob, (unsigned long long)pt);
   f32x4 *row = reinterpret_cast<f32x4 *>(X + 8 * i);
-  row[0] = f32x4{(float)((px - xm0) / xs0), (float)((py - xm1) / xs1), (float)((pz - xm2) / xs2),
-                 0.0f};
+  // bounded: the first layer is tanh / sigmoid (ann_input)
+  row[0] = f32x4{ann_input((px - xm0) / xs0, bounded), ann_input((py - xm1) / xs1, bounded),
+                 ann_input((pz - xm2) / xs2, bounded), 0.0f};
   row[1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 }
 
@@ -500,7 +502,7 @@ __global__ __launch_bounds__(256) void annb_out_kernel(const float *__restrict__
       const double err = fk_error(o.jc, th, pts[3 * pt], pts[3 * pt + 1], pts[3 * pt + 2],
                                   o.alpha_bad);
       fk_err[pt] = err;
-      e = (err == err) ? err : 0.0;
+      e = (err < __builtin_inf()) ? err : 0.0;  // finite ones (not NaN, inf)
     }
   }
   if (fk_err) wave_fk_stats(S, e, e);
@@ -541,6 +543,7 @@ void launch_ann_big(const AnnBigModel &m, const RobotDev &r, const double *pts, 
     kt_begin("annb_in_kernel", st);
     IK_LAUNCH(annb_in_kernel, dim3(g1), dim3(256), 0, st, pts, p0, rows, m.xm[0],
                        m.xm[1], m.xm[2], m.xs[0], m.xs[1], m.xs[2], r, check_limits ? 1 : 0,
+                       (m.layers[0].act == IK_ACT_TANH || m.layers[0].act == IK_ACT_SIGMOID) ? 1 : 0,
                        buf[0], S);
     kt_end(st);
     int cur = 0, lda = 8;

@@ -946,9 +946,10 @@ ann_fused_kernel(AnnArgs a) {
         pz = a.pts[3 * pt + 2];
         if (a.check_limits && outside(a.r.lim, px, py, pz))
           atomicMin(&a.S->first_oob, (unsigned long long)pt);
-        x0 = (float)((px - a.m.xm[0]) / a.m.xs[0]);
-        x1 = (float)((py - a.m.xm[1]) / a.m.xs[1]);
-        x2 = (float)((pz - a.m.xm[2]) / a.m.xs[2]);
+        const bool bounded = a.m.act[0] == IK_ACT_TANH || a.m.act[0] == IK_ACT_SIGMOID;
+        x0 = ann_input((px - a.m.xm[0]) / a.m.xs[0], bounded);
+        x1 = ann_input((py - a.m.xm[1]) / a.m.xs[1], bounded);
+        x2 = ann_input((pz - a.m.xm[2]) / a.m.xs[2], bounded);
       }
       f32x4 *row = reinterpret_cast<f32x4 *>(H + hrow<LY>(tid));
       row[0] = f32x4{x0, x1, x2, 0.0f};
@@ -1043,7 +1044,7 @@ ann_fused_kernel(AnnArgs a) {
         }
       }
       if (a.fk_err) {
-        double e = (valid && err == err) ? err : 0.0;
+        double e = (valid && err < __builtin_inf()) ? err : 0.0;  // finite ones (not NaN, inf)
         blk_max = fmax(blk_max, e);
         blk_sum += e;
       }

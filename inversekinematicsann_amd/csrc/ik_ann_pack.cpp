@@ -99,15 +99,17 @@ size_t ann_h_bytes(int k, int n) { return frag16_elems(k, n) * 4; }
 
 // The power of two that brings the layer's largest |weight| to [2^13, 2^14):
 // the fp16 planes then keep their full 11 bits down to weights ~2^-10 of the
-// largest, and nothing comes near fp16's 65504.
+// largest, and nothing comes near fp16's 65504.  Not clamped: an exponent past
+// +-kAnnHMaxScaleExp means no fp16x3 operand (ann_pack_section), since a clamped
+// one would leave the largest weights above 65504 (inf planes) or, at the other
+// end, in fp16's subnormals.
 int ann_h_scale_exp(const float *W, int k, int n) {
   float mx = 0.0f;
   for (size_t i = 0; i < (size_t)k * n; ++i) mx = std::fmax(mx, std::fabs(W[i]));
   if (!(mx > 0.0f) || !std::isfinite(mx)) return 0;
   int e = 0;
   std::frexp(mx, &e);  // mx in [2^(e-1), 2^e)
-  int s = 14 - e;
-  return s < -60 ? -60 : (s > 60 ? 60 : s);
+  return 14 - e;
 }
 
 // The fp16x3 weight operand: planes (hi, lo) of W * 2^scale_exp in pack_frag16's
@@ -169,7 +171,9 @@ AnnLayout::AnnLayout(int n, const int32_t *d, const int32_t *acts, bool planes)
   if (big) act_min = 2 * 128 * ld * sizeof(float);
 }
 
-int ann_pack_section(const AnnLayout &L, int l, const float *W, const float *b, char *dst) {
+int ann_pack_section(const AnnLayout &L, int l, const float *W, const float *b, char *dst,
+                     bool *h_built) {
+  if (h_built) *h_built = false;
   const int k = L.dims[l], n = L.dims[l + 1];
   const size_t at = L.woff[l];
   ann_pack_layer(W, k, n, reinterpret_cast<float *>(dst));
@@ -180,7 +184,9 @@ int ann_pack_section(const AnnLayout &L, int l, const float *W, const float *b, 
   }
   if (!L.halvable[l]) return 0;
   const int e = ann_h_scale_exp(W, k, n);
+  if (e < -kAnnHMaxScaleExp || e > kAnnHMaxScaleExp) return 0;  // the layer stays fp32
   ann_pack_layer_h(W, k, n, e, dst + (L.hoff[l] - at));
+  if (h_built) *h_built = true;
   return e;
 }
 

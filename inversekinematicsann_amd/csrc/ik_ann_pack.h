@@ -24,6 +24,10 @@ size_t ann_x_bytes(int k, int n);  // bytes of one layer's bf16x6 weight operand
 void ann_pack_layer_x(const float *W, int k, int n, void *dst);
 size_t ann_h_bytes(int k, int n);  // bytes of one layer's fp16x3 weight operand
 int ann_h_scale_exp(const float *W, int k, int n);  // the weight pre-scale exponent
+// The pre-scale exponents an fp16x3 operand is built for: 2^-e and the scaled
+// bias stay well inside fp32.  Largest |w| from ~2^-47 to ~2^74; a layer outside
+// runs fp32 in fp16x3 mode.
+constexpr int kAnnHMaxScaleExp = 60;
 void ann_pack_layer_h(const float *W, int k, int n, int scale_exp, void *dst);
 // the layered path's bf16x6 weight planes: [plane][ceil(k / 32)][n rounded up to
 // 128][32] bf16, ann_big_x_bytes(k, n) bytes
@@ -57,6 +61,9 @@ struct AnnLayout {
 };
 // Layer l's section into dst (section_bytes(l), zeroed by the caller); returns
 // the fp16x3 weight pre-scale exponent (0 for a layer that is not halvable).
-int ann_pack_section(const AnnLayout &L, int l, const float *W, const float *b, char *dst);
+// h_built: whether the fp16x3 planes were written -- not for a halvable layer
+// whose exponent is outside +-kAnnHMaxScaleExp (its planes stay zero, unused).
+int ann_pack_section(const AnnLayout &L, int l, const float *W, const float *b, char *dst,
+                     bool *h_built = nullptr);
 
 }  // namespace ikhip

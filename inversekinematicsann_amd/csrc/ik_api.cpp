@@ -731,11 +731,14 @@ int ik_ann_load(ik_ctx *c, int n_layers, const int32_t *dims, const int32_t *act
   // at most the largest layer's packed bytes, and an allocation failure is an
   // error code, not an exception leaving the C ABI
   std::vector<int> hexp(n_layers, 0);
+  std::vector<char> hbuilt(n_layers, 0);
   try {
     std::vector<char> host;
     for (int l = 0; l < n_layers; ++l) {
       host.assign(L.section_bytes(l), 0);
-      hexp[l] = ann_pack_section(L, l, W[l], b[l], host.data());
+      bool built = false;
+      hexp[l] = ann_pack_section(L, l, W[l], b[l], host.data(), &built);
+      hbuilt[l] = built;
       IK_HIP(hipMemcpy(base + L.woff[l], host.data(), host.size(), hipMemcpyHostToDevice));
     }
   } catch (const std::bad_alloc &) {
@@ -768,7 +771,8 @@ int ik_ann_load(ik_ctx *c, int n_layers, const int32_t *dims, const int32_t *act
     m.wp[l] = reinterpret_cast<const float4 *>(wp);
     m.bias[l] = bias;
     c->ann_wx[l] = wx;
-    c->ann_wh[l] = L.halvable[l] ? base + L.hoff[l] : nullptr;
+    // (no planes for a layer whose weights are out of the pre-scale's range: fp32)
+    c->ann_wh[l] = hbuilt[l] ? base + L.hoff[l] : nullptr;
     c->ann_hinv[l] = std::ldexp(1.0f, -hexp[l]);
   }
   c->ann_loaded = true;

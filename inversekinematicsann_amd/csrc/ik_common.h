@@ -238,6 +238,16 @@ __device__ __forceinline__ void sincos_fk(double x, double *sp, double *cp) {
   *cp = ((q + 1) & 2) ? -cc : cc;
 }
 
+// A scaled ANN input that overflowed fp32 (a point ~1e39 scales away) in front of
+// a bounded first layer (tanh / sigmoid): +-FLT_MAX saturates every real column
+// exactly as +-inf would, but times the zero weights of the padded columns it is
+// 0, not inf * 0 = NaN, which the next layer's padded K would spread over the row.
+// NaN stays NaN.  In front of relu / linear the infinity itself goes in.
+__device__ __forceinline__ float ann_input(double x, bool bounded) {
+  const float v = (float)x;
+  return (bounded && fabsf(v) == __builtin_inff()) ? copysignf(3.402823466e38f, v) : v;
+}
+
 __device__ __forceinline__ bool angle_ok(double a) { return !((a < -2 * kPi) || (a > 2 * kPi)); }
 
 __device__ __forceinline__ void dh_transform(double th, double eps, double a, double al,

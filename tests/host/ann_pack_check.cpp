@@ -182,6 +182,52 @@ static void check_h_exponent_edges() {
   CHECK(ann_h_scale_exp(W.data(), 33, 40) == 0, "layer with inf: exponent not 0");
 }
 
+// The largest |w| of a halvable layer swept over 2^-100 .. 2^100 (times 1.9995,
+// the mantissa that rounds up first), the other weights down to 2^-12 of it,
+// through ann_pack_section.  While the pre-scale exponent is within
+// +-kAnnHMaxScaleExp the planes are built, finite, and hi + lo is the scaled
+// weight to 2^-21 of the largest; past it they are not built (the section stays
+// zero and the layer runs fp32) -- a clamped exponent would leave the largest
+// weights above fp16's 65504 from 2^75 on.
+static void check_h_scale_sweep() {
+  const int32_t dims[] = {3, 33, 40, 4}, acts[] = {IK_ACT_TANH, IK_ACT_TANH, IK_ACT_LINEAR};
+  const AnnLayout L(3, dims, acts, true);
+  CHECK(L.halvable[1], "sweep layout: layer 1 not halvable");
+  const int k = 33, n = 40, G32 = 2;
+  const std::vector<float> b(n, 0.0f);
+  std::mt19937 rng(77);
+  std::uniform_real_distribution<float> ud(-12.0f, 0.0f);
+  for (int E = -100; E <= 100; ++E) {
+    std::vector<float> W((size_t)k * n);
+    for (float &w : W) w = std::ldexp(((rng() & 1) ? -1.0f : 1.0f) * std::exp2(ud(rng)), E);
+    W[5 * n + 7] = std::ldexp(-1.9995f, E);
+    W[32 * n + 39] = std::ldexp(1.9995f, E);
+    std::unique_ptr<char[]> sec(new char[L.section_bytes(1)]());
+    bool built = true;
+    const int s = ann_pack_section(L, 1, W.data(), b.data(), sec.get(), &built);
+    const bool inside = 13 - E >= -kAnnHMaxScaleExp && 13 - E <= kAnnHMaxScaleExp;
+    CHECK(built == inside, "sweep 2^%d: planes %s", E, built ? "built" : "not built");
+    CHECK(s == (inside ? 13 - E : 0), "sweep 2^%d: exponent %d", E, s);
+    const _Float16 *d = reinterpret_cast<const _Float16 *>(sec.get() + (L.hoff[1] - L.woff[1]));
+    const size_t cnt = ann_h_bytes(k, n) / 2;
+    std::vector<double> hi(W.size(), 0.0), lo(W.size(), 0.0);
+    for (size_t e = 0; e < cnt; ++e) {
+      const float v = (float)d[e];
+      CHECK(std::isfinite(v), "sweep 2^%d: element %zu is %g", E, e, v);
+      CHECK(built || v == 0.0f, "sweep 2^%d: planes not built but element %zu is %g", E, e, v);
+      const Frag16 f = decode16(e, 2, G32);
+      if (f.kk < k && f.c < n) (f.p ? lo : hi)[(size_t)f.kk * n + f.c] = v;
+    }
+    if (!built) continue;
+    const double mx = std::ldexp(1.9995, E + s);
+    for (size_t i = 0; i < W.size(); ++i) {
+      const double x = std::ldexp((double)W[i], s);
+      CHECK(std::fabs(x - (hi[i] + lo[i])) <= mx * 0x1p-21, "sweep 2^%d W[%zu]: |x - (hi + lo)| = %g",
+            E, i, std::fabs(x - (hi[i] + lo[i])));
+    }
+  }
+}
+
 // The operands of a layout, in address order: ascending, aligned, disjoint.
 static void check_sections(const char *what, const AnnLayout &L) {
   size_t end = 0;
@@ -294,6 +340,7 @@ int main() {
     for (const auto &s : big_shapes) check_big_x(s[0], s[1], dist);
   }
   check_h_exponent_edges();
+  check_h_scale_sweep();
   check_layout();
   if (g_fail) {
     std::printf("%d checks failed\n", g_fail);
