@@ -286,6 +286,27 @@ int ik_ann_effective_mode(ik_ctx *ctx);
 int ik_ann_train_begin(ik_ctx *ctx, int n_layers, const int32_t *dims, const int32_t *acts,
                        const float *const *W, const float *const *b, int max_batch, double lr,
                        double beta1, double beta2, double eps);
+/* loss = mse_weight * mse + fk_weight * fk for every later step / grads / epoch call
+ * of this training state (default 1, 0: the reference's 'mse'). The four scaler
+ * arrays (3, 3, 4, 4 doubles, host) are copied; they may be NULL when fk_weight == 0.
+ * fk is the mean over the batch's rows of e . e, e = FK(wrap(theta)) - p in float64:
+ * theta_j = a_j y_scale_j + y_mean_j from the last layer's fp32 outputs a,
+ * p_k = x_k x_scale_k + x_mean_k from the row's scaled fp32 inputs, FK the chain of
+ * the context's robot (NaN when some |alpha_i| > 2 pi), wrap(t) = t - 2 pi rint(t /
+ * 2 pi) as in ik_refine.  Its gradient reaches the last layer as fk_weight (2 / rows)
+ * (J_j . e) y_scale_j, J the analytic Jacobian, added to the mse's in float64 and
+ * rounded to fp32 once.  With fk_weight > 0 one kernel replaces the loss kernel: no
+ * launch is added to a step.  IK_E_BADARG (the state unchanged): before
+ * ik_ann_train_begin; a negative or non-finite weight; both weights 0; with
+ * fk_weight > 0, dims[0] != 3, dims[n_layers] != 4, a NULL scaler array, a non-finite
+ * scaler entry or a scale of 0.  ik_ann_train_begin resets the loss to (1, 0). */
+int ik_ann_train_set_loss(ik_ctx *ctx, double mse_weight, double fk_weight,
+                          const double *x_mean, const double *x_scale,
+                          const double *y_mean, const double *y_scale);
+/* The fk term (mean squared FK error) of the last ik_ann_train_step / _grads call
+ * (val_fk NaN) or of the last ik_ann_train_epoch: the steps' values weighted by their
+ * rows, and the validation rows' mean (NaN without any). Both NaN while fk_weight == 0. */
+int ik_ann_train_fk(ik_ctx *ctx, double *train_fk, double *val_fk);
 /* The data set, already scaled: x n_train x dims[0], y n_train x dims[n_layers], and
  * the validation rows (n_val may be 0). */
 int ik_ann_train_data(ik_ctx *ctx, const float *x, const float *y, int64_t n_train,

@@ -47,7 +47,7 @@ EXPORTED_SYMBOLS = ("ik_ctx_create", "ik_ctx_destroy", "ik_ctx_set_stream", "ik_
                     "ik_comm_loopback_stall", "ik_fabrik_order_get", "ik_fabrik_order_set",
                     "ik_ann_train_begin", "ik_ann_train_data", "ik_ann_train_grads",
                     "ik_ann_train_step", "ik_ann_train_epoch", "ik_ann_train_get",
-                    "ik_ann_train_end")
+                    "ik_ann_train_end", "ik_ann_train_set_loss", "ik_ann_train_fk")
 ANN_MODES = {"fp32": 0, "bf16x6": 1, "fp16x3": 2}
 
 
@@ -185,6 +185,8 @@ def load_library(path: str = LIB_PATH):
         L.ik_ann_train_epoch.argtypes = [vp, ip, ctypes.c_int, pd, pd]
         L.ik_ann_train_get.argtypes = [vp, ctypes.c_int, pp, pp]
         L.ik_ann_train_end.argtypes = [vp]
+        L.ik_ann_train_set_loss.argtypes = [vp, ctypes.c_double, ctypes.c_double, dp, dp, dp, dp]
+        L.ik_ann_train_fk.argtypes = [vp, pd, pd]
         _lib = L
         return L
 
@@ -612,6 +614,26 @@ class Context:
         self._check(self.lib.ik_ann_train_begin(self.handle, *stack, int(max_batch), float(lr),
                                                 float(beta1), float(beta2), float(eps)))
         self._train_dims = dims
+
+    def train_set_loss(self, mse_weight: float = 1.0, fk_weight: float = 0.0, x_scaler=None,
+                       y_scaler=None):
+        """ik_ann_train_set_loss: loss = mse_weight * mse + fk_weight * fk for the later
+        steps; x_scaler / y_scaler are (mean, scale) pairs, needed when fk_weight > 0."""
+        arrs = []
+        for sc, n in ((x_scaler, 3), (y_scaler, 4)):
+            for a in (sc if sc is not None else (None, None)):
+                arrs.append(None if a is None else _host(a, np.float64).reshape(-1))
+                if arrs[-1] is not None and arrs[-1].shape[0] != n:
+                    raise ValueError(f"a scaler array of {arrs[-1].shape[0]} entries, expected {n}")
+        self._check(self.lib.ik_ann_train_set_loss(self.handle, float(mse_weight),
+                                                   float(fk_weight), *[_ptr(a) for a in arrs]))
+
+    def train_fk(self):
+        """ik_ann_train_fk: (train_fk, val_fk), the mean squared FK error of the last
+        step / grads call or epoch (NaN while fk_weight == 0)."""
+        tf, vf = ctypes.c_double(), ctypes.c_double()
+        self._check(self.lib.ik_ann_train_fk(self.handle, ctypes.byref(tf), ctypes.byref(vf)))
+        return tf.value, vf.value
 
     def _train_xy(self, x, y):
         d = getattr(self, "_train_dims", None)

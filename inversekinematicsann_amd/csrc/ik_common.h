@@ -673,8 +673,14 @@ struct TrainDev {
   float *A[kTrainMaxLayers + 1] = {};  // A[0]: staged inputs; A[l]: layer l's outputs of the batch
   float *y = nullptr;                  // staged targets
   float *dZ[2] = {};                   // max_batch x widest layer, alternating
-  double *loss = nullptr;              // loss-sum slots (one per step / validation chunk)
+  // loss-sum slots (one per step / validation chunk): 2 loss_slots doubles -- a double
+  // a slot, or with the fk term two, {squared errors' sum, fk sum}
+  double *loss = nullptr;
   int64_t loss_slots = 0;
+  // the loss (ik_ann_train_set_loss): mse_weight * mse + fk_weight * fk
+  double mse_weight = 1.0, fk_weight = 0.0;
+  TrainFkScale fk_scale = {};
+  double last_train_fk = __builtin_nan(""), last_val_fk = __builtin_nan("");  // ik_ann_train_fk
   void *block = nullptr;               // the allocation the pointers above the slots point into
   double lr = 0, beta1 = 0, beta2 = 0, eps = 0;
   int64_t t = 0;                       // Adam steps taken
@@ -686,9 +692,15 @@ struct TrainDev {
 };
 // A_l = act(A_{l-1} W_l + b_l) for every layer; x: rows x dims[0] device floats.
 void train_forward(const TrainDev &T, const float *x, int rows, hipStream_t st);
-// *slot = sum((A_L - y)^2) in float64; with want_dz, dZ[0] = 2 (A_L - y) / (rows n_out) * act'(A_L).
+// *slot = sum((A_L - y)^2) in float64; with want_dz, dZ[0] = mse_weight 2 (A_L - y) /
+// (rows n_out) * act'(A_L).
 void train_loss(const TrainDev &T, const float *y, int rows, double *slot, bool want_dz,
                 hipStream_t st);
+// The loss with the forward-kinematics term (fk_weight > 0; ik_train_fk_row.h): also
+// *fk_slot = sum(e . e) over the rows, e = FK(wrap(theta)) - p of the robot rc from the
+// outputs A_L and the inputs x (rows x 3, device), and dZ[0] of the weighted sum.
+void train_loss_fk(const TrainDev &T, const RobotConstDev *rc, const float *x, const float *y,
+                   int rows, double *slot, double *fk_slot, bool want_dz, hipStream_t st);
 // The backward pass from dZ[0]: with adam, W / b / m / v are updated in the weight-
 // gradient kernels' epilogues; without, the gradients go to gW / gb.
 void train_backward(const TrainDev &T, const float *x, int rows, bool adam, const AdamDev &ad,

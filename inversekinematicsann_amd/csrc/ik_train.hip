@@ -5,6 +5,8 @@
 // loss='mse' and Adam: per step
 //   train_gemm_kernel<FWD>    A_l = act(A_{l-1} W_l + b_l)              (NN, per layer)
 //   train_loss_kernel         dZ_L = 2 (A_L - Y) / (rows n_out) act'(A_L), loss sum (float64)
+//     (train_loss_fk_kernel in its place once ik_ann_train_set_loss gave the forward-
+//      kinematics term a weight: also sum |FK(theta) - p|^2 and its gradient in dZ_L)
 //   train_gemm_kernel<DGRAD>  dZ_{l-1} = (dZ_l W_l^T) act'(A_{l-1})      (NT, layers > 1)
 //   train_gemm_kernel<WADAM>  [G; g] = [A_{l-1}, 1]^T dZ_l, then Adam on W, b, m, v
 //                                                                        (TN, per layer)
@@ -30,6 +32,7 @@
 
 #include "ik_act.h"
 #include "ik_common.h"
+#include "ik_train_fk_row.h"
 
 namespace ikhip {
 namespace train {
@@ -171,6 +174,69 @@ __global__ __launch_bounds__(256) void train_loss_kernel(const float *__restrict
   if (tid == 0) *slot = sh[0];
 }
 
+// The loss with the forward-kinematics term (ik_ann_train_set_loss with fk_weight > 0):
+// loss = mse_weight mse + fk_weight fk, fk the mean of e . e over the rows,
+// e = FK(wrap(theta)) - p (ik_train_fk_row.h).  One workgroup as above; thread t takes
+// rows t, t + 256, ..., a row's arithmetic float64 in registers, the robot's constants
+// wave-uniform from the constant address space.  dZ_L is evaluated in float64 and
+// rounded once.  Two sums, the squared errors' and the e . e's, through the same fixed
+// tree: the same bits on every run.
+struct LossFkArgs {
+  const RobotConstDev *rc;
+  const float *A, *X, *Y;  // rows x 4 outputs, rows x 3 inputs, rows x 4 labels
+  int rows, act;
+  double cm, cf;  // dZ's factors of (a_j - y_j) and of (J_j . e) y_scale_j
+  TrainFkScale sc;
+  float *dZ;             // rows x 4, or null
+  double *slot, *fk_slot;
+};
+
+__global__ __launch_bounds__(256) void train_loss_fk_kernel(LossFkArgs g) {
+  __shared__ double sh[2][256];
+  const RcConst k = (RcConst)g.rc;
+  const int tid = threadIdx.x;
+  double jc[14];
+#pragma unroll
+  for (int i = 0; i < 14; ++i) jc[i] = k->jc[i];
+  const bool alpha_ok = !k->alpha_bad;
+  double sm = 0.0, sf = 0.0;
+  for (int r = tid; r < g.rows; r += 256) {
+    const float4 a4 = *reinterpret_cast<const float4 *>(g.A + 4 * (int64_t)r);
+    const float4 y4 = *reinterpret_cast<const float4 *>(g.Y + 4 * (int64_t)r);
+    const float a[4] = {a4.x, a4.y, a4.z, a4.w}, y[4] = {y4.x, y4.y, y4.z, y4.w};
+    const float x[3] = {g.X[3 * (int64_t)r], g.X[3 * (int64_t)r + 1], g.X[3 * (int64_t)r + 2]};
+    double th[4], s[4], c[4];
+    train_fk_angles(g.sc, a, th);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sincos_fk(th[j], &s[j], &c[j]);
+    const TrainFkRow o = train_fk_row(jc, g.sc, s, c, x, alpha_ok);
+    sf += o.ee;
+    float dz[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const double d = (double)a[j] - (double)y[j];
+      sm += d * d;
+      dz[j] = (float)((g.cm * d + g.cf * o.je[j] * g.sc.ys[j]) * (double)act_deriv(g.act, a[j]));
+    }
+    if (g.dZ)
+      *reinterpret_cast<float4 *>(g.dZ + 4 * (int64_t)r) = make_float4(dz[0], dz[1], dz[2], dz[3]);
+  }
+  sh[0][tid] = sm;
+  sh[1][tid] = sf;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) {
+      sh[0][tid] += sh[0][tid + w];
+      sh[1][tid] += sh[1][tid + w];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    *g.slot = sh[0][0];
+    *g.fk_slot = sh[1][0];
+  }
+}
+
 // The epoch's shuffle: row i of the permuted copies is row perm[i] of the data.
 __global__ __launch_bounds__(256) void train_gather_kernel(
     const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ perm,
@@ -217,10 +283,28 @@ void train_loss(const TrainDev &T, const float *y, int rows, double *slot, bool 
                 hipStream_t st) {
   using namespace train;
   const int L = T.n_layers, n = T.dims[L];
-  const float scale = (float)(2.0 / ((double)rows * (double)n));
+  const float scale = (float)train_dz_mse_factor(T.mse_weight, rows, n);
   kt_begin("train_loss_kernel", st);
   IK_LAUNCH(train_loss_kernel, dim3(1), dim3(256), 0, st, T.A[L], y, rows * n, T.act[L - 1],
             scale, want_dz ? T.dZ[0] : nullptr, slot);
+  kt_end(st);
+}
+
+void train_loss_fk(const TrainDev &T, const RobotConstDev *rc, const float *x, const float *y,
+                   int rows, double *slot, double *fk_slot, bool want_dz, hipStream_t st) {
+  using namespace train;
+  const int L = T.n_layers;  // dims[0] == 3 and dims[L] == 4 (ik_ann_train_set_loss)
+  LossFkArgs g = {};
+  g.rc = rc;
+  g.A = T.A[L], g.X = x, g.Y = y;
+  g.rows = rows, g.act = T.act[L - 1];
+  g.cm = train_dz_mse_factor(T.mse_weight, rows, 4);
+  g.cf = train_dz_fk_factor(T.fk_weight, rows);
+  g.sc = T.fk_scale;
+  g.dZ = want_dz ? T.dZ[0] : nullptr;
+  g.slot = slot, g.fk_slot = fk_slot;
+  kt_begin("train_loss_fk_kernel", st);
+  IK_LAUNCH(train_loss_fk_kernel, dim3(1), dim3(256), 0, st, g);
   kt_end(st);
 }
 

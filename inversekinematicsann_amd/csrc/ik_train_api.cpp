@@ -4,6 +4,7 @@
 // refused arguments are the host-only ik_train_plan.cpp.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <new>
 #include <string>
@@ -35,9 +36,21 @@ int train_slots(ik_ctx *c, int64_t want) {
   if (T->loss) IK_HIP(hipFree(T->loss));
   T->loss = nullptr;
   T->loss_slots = 0;
-  IK_HIP(hipMalloc(reinterpret_cast<void **>(&T->loss), (size_t)want * sizeof(double)));
+  // two doubles a slot: with the fk term a slot is {squared errors' sum, fk sum}, so one
+  // copy brings both back; without it the sums lie one double apart as they always did
+  IK_HIP(hipMalloc(reinterpret_cast<void **>(&T->loss), 2 * (size_t)want * sizeof(double)));
   T->loss_slots = want;
   return IK_OK;
+}
+
+// The loss kernel of the rows x (device), labels y, into slot `at`.
+void loss_launch(ik_ctx *c, const float *x, const float *y, int rows, int64_t at, bool want_dz) {
+  const TrainDev *T = c->train;
+  if (T->fk_weight > 0.0)
+    train_loss_fk(*T, c->rconst, x, y, rows, T->loss + 2 * at, T->loss + 2 * at + 1, want_dz,
+                  c->stream);
+  else
+    train_loss(*T, y, rows, T->loss + at, want_dz, c->stream);
 }
 
 // One batch from host rows: forward, loss, backward (Adam update or gradients out).
@@ -56,14 +69,20 @@ int train_batch(ik_ctx *c, const char *who, const float *x, const float *y, int 
   IK_HIP(hipMemcpyAsync(T->y, y, (size_t)rows * dL * sizeof(float), hipMemcpyHostToDevice,
                         c->stream));
   train_forward(*T, T->A[0], rows, c->stream);
-  train_loss(*T, T->y, rows, T->loss, true, c->stream);
+  loss_launch(c, T->A[0], T->y, rows, 0, true);
   train_backward(*T, T->A[0], rows, adam, next_adam(T), c->stream);
   IK_HIP(hipGetLastError());
-  double sum = 0.0;
-  IK_HIP(hipMemcpyAsync(&sum, T->loss, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  const bool fk = T->fk_weight > 0.0;
+  double sum[2] = {0.0, 0.0};  // {squared errors, fk}
+  IK_HIP(hipMemcpyAsync(sum, T->loss, (fk ? 2 : 1) * sizeof(double), hipMemcpyDeviceToHost,
+                        c->stream));
   IK_HIP(hipStreamSynchronize(c->stream));
   if (adam) T->t += 1;
-  if (loss) *loss = sum / ((double)rows * (double)dL);
+  T->last_train_fk = fk ? sum[1] / (double)rows : std::nan("");
+  T->last_val_fk = std::nan("");
+  if (loss)
+    *loss = train_total_loss(T->mse_weight, T->fk_weight, sum[0] / ((double)rows * (double)dL),
+                             T->last_train_fk);
   return IK_OK;
 }
 
@@ -133,6 +152,33 @@ int ik_ann_train_begin(ik_ctx *c, int n_layers, const int32_t *dims, const int32
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess)
     return bail(fail(IK_E_HIP, std::string("ik_ann_train_begin: ") + hipGetErrorString(e)));
+  return IK_OK;
+}
+
+int ik_ann_train_set_loss(ik_ctx *c, double mse_weight, double fk_weight, const double *x_mean,
+                          const double *x_scale, const double *y_mean, const double *y_scale) {
+  if (!c) return fail(IK_E_BADARG, "ik_ann_train_set_loss: NULL context");
+  TrainDev *T = c->train;
+  const std::string why =
+      train_set_loss_refusal(T != nullptr, T ? T->dims[0] : 0, T ? T->dims[T->n_layers] : 0,
+                             mse_weight, fk_weight, x_mean, x_scale, y_mean, y_scale);
+  if (!why.empty()) return fail(IK_E_BADARG, "ik_ann_train_set_loss: " + why);
+  T->mse_weight = mse_weight, T->fk_weight = fk_weight;
+  if (fk_weight > 0.0)
+    for (int i = 0; i < 4; ++i) {
+      if (i < 3) T->fk_scale.xm[i] = x_mean[i], T->fk_scale.xs[i] = x_scale[i];
+      T->fk_scale.ym[i] = y_mean[i], T->fk_scale.ys[i] = y_scale[i];
+    }
+  T->last_train_fk = T->last_val_fk = std::nan("");
+  return IK_OK;
+}
+
+int ik_ann_train_fk(ik_ctx *c, double *train_fk, double *val_fk) {
+  if (!c) return fail(IK_E_BADARG, "ik_ann_train_fk: NULL context");
+  const TrainDev *T = c->train;
+  if (!T) return fail(IK_E_BADARG, "ik_ann_train_fk: before ik_ann_train_begin");
+  if (train_fk) *train_fk = T->last_train_fk;
+  if (val_fk) *val_fk = T->last_val_fk;
   return IK_OK;
 }
 
@@ -220,7 +266,7 @@ int ik_ann_train_epoch(ik_ctx *c, const int32_t *perm, int batch, double *train_
     const int64_t r0 = ep.step_row(s);
     const int rows = ep.step_rows(s);
     train_forward(*T, xs + r0 * d0, rows, c->stream);
-    train_loss(*T, ys + r0 * dL, rows, T->loss + s, true, c->stream);
+    loss_launch(c, xs + r0 * d0, ys + r0 * dL, rows, s, true);
     train_backward(*T, xs + r0 * d0, rows, true, next_adam(T), c->stream);
     T->t += 1;
   }
@@ -229,17 +275,26 @@ int ik_ann_train_epoch(ik_ctx *c, const int32_t *perm, int batch, double *train_
     const int64_t r0 = ep.chunk_row(v);
     const int rows = ep.chunk_rows(v);
     train_forward(*T, T->Xv + r0 * d0, rows, c->stream);
-    train_loss(*T, T->Yv + r0 * dL, rows, T->loss + ep.steps + v, false, c->stream);
+    loss_launch(c, T->Xv + r0 * d0, T->Yv + r0 * dL, rows, ep.steps + v, false);
   }
   IK_HIP(hipGetLastError());
-  std::vector<double> sums((size_t)ep.slots());
+  const bool fk = T->fk_weight > 0.0;
+  std::vector<double> sums((size_t)ep.slots() * (fk ? 2 : 1)), fsums;
   IK_HIP(hipMemcpyAsync(sums.data(), T->loss, sums.size() * sizeof(double), hipMemcpyDeviceToHost,
                         c->stream));
   IK_HIP(hipStreamSynchronize(c->stream));
+  if (fk) {  // {squared errors, fk} pairs apart
+    fsums.resize((size_t)ep.slots());
+    for (size_t i = 0; i < fsums.size(); ++i) fsums[i] = sums[2 * i + 1], sums[i] = sums[2 * i];
+  }
   double tl, vl;
   train_epoch_losses(ep, (int)dL, sums.data(), &tl, &vl);
-  if (train_loss_out) *train_loss_out = tl;
-  if (val_loss_out) *val_loss_out = vl;
+  T->last_train_fk = T->last_val_fk = std::nan("");
+  if (fk) train_epoch_fk(ep, fsums.data(), &T->last_train_fk, &T->last_val_fk);
+  if (train_loss_out)
+    *train_loss_out = train_total_loss(T->mse_weight, T->fk_weight, tl, T->last_train_fk);
+  if (val_loss_out)
+    *val_loss_out = train_total_loss(T->mse_weight, T->fk_weight, vl, T->last_val_fk);
   return IK_OK;
 }
 

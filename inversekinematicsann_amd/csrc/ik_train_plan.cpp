@@ -107,4 +107,52 @@ std::string train_epoch_refusal(const int32_t *perm, int64_t n_train, int batch,
   return "";
 }
 
+std::string train_set_loss_refusal(bool begun, int d0, int dL, double mse_weight,
+                                   double fk_weight, const double *x_mean, const double *x_scale,
+                                   const double *y_mean, const double *y_scale) {
+  if (!begun) return "before ik_ann_train_begin";
+  if (!std::isfinite(mse_weight) || !std::isfinite(fk_weight) || mse_weight < 0.0 ||
+      fk_weight < 0.0)
+    return "the weights must be finite and not negative";
+  if (mse_weight == 0.0 && fk_weight == 0.0) return "both weights are 0";
+  if (!(fk_weight > 0.0)) return "";
+  if (d0 != 3 || dL != 4)
+    return "the fk term needs 3 inputs and 4 outputs, the network has " + std::to_string(d0) +
+           " and " + std::to_string(dL);
+  if (!x_mean || !x_scale || !y_mean || !y_scale) return "NULL scaler array";
+  const double *arr[4] = {x_mean, x_scale, y_mean, y_scale};
+  const char *name[4] = {"x_mean", "x_scale", "y_mean", "y_scale"};
+  for (int k = 0; k < 4; ++k)
+    for (int i = 0; i < (k < 2 ? 3 : 4); ++i) {
+      if (!std::isfinite(arr[k][i]))
+        return std::string(name[k]) + "[" + std::to_string(i) + "] is not finite";
+      if ((k & 1) && arr[k][i] == 0.0)
+        return std::string(name[k]) + "[" + std::to_string(i) + "] is 0";
+    }
+  return "";
+}
+
+double train_dz_mse_factor(double mse_weight, int rows, int dL) {
+  return mse_weight * 2.0 / ((double)rows * (double)dL);
+}
+
+double train_dz_fk_factor(double fk_weight, int rows) { return fk_weight * 2.0 / (double)rows; }
+
+double train_total_loss(double mse_weight, double fk_weight, double mse, double fk) {
+  const double m = mse_weight * mse;
+  return fk_weight > 0.0 ? m + fk_weight * fk : m;
+}
+
+void train_epoch_fk(const TrainEpoch &e, const double *sums, double *train_fk, double *val_fk) {
+  double acc = 0.0;
+  for (int64_t s = 0; s < e.steps; ++s) {
+    const double rows = (double)e.step_rows(s);
+    acc += sums[s] / rows * rows;
+  }
+  *train_fk = acc / (double)e.n_train;
+  double vs = 0.0;
+  for (int64_t v = 0; v < e.vchunks; ++v) vs += sums[e.steps + v];
+  *val_fk = e.n_val > 0 ? vs / (double)e.n_val : std::nan("");
+}
+
 }  // namespace ikhip

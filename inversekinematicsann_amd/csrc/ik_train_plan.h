@@ -74,4 +74,27 @@ std::string train_begin_refusal(int n_layers, const int32_t *dims, const int32_t
 std::string train_data_refusal(int64_t n_train, int64_t n_val);
 std::string train_epoch_refusal(const int32_t *perm, int64_t n_train, int batch, int max_batch);
 
+// ---- the loss (ik_ann_train_set_loss): mse_weight * mse + fk_weight * fk ----------
+// The scalers the forward-kinematics term decodes a row with (ik_train_fk_row.h):
+// position = x * xs + xm, theta = a * ys + ym.
+struct TrainFkScale {
+  double xm[3], xs[3], ym[4], ys[4];
+};
+// "" or the text after "ik_ann_train_set_loss: ".  begun: a training state exists;
+// d0 / dL: its first and last widths.  The scaler arrays are read only when
+// fk_weight > 0.
+std::string train_set_loss_refusal(bool begun, int d0, int dL, double mse_weight,
+                                   double fk_weight, const double *x_mean, const double *x_scale,
+                                   const double *y_mean, const double *y_scale);
+// The loss kernel's factors of (a_j - y_j) and of (J_j . e) y_scale_j in dZ_L:
+// mse_weight 2 / (rows dL) and fk_weight 2 / rows.
+double train_dz_mse_factor(double mse_weight, int rows, int dL);
+double train_dz_fk_factor(double fk_weight, int rows);
+// What the calls return as the loss: mse_weight * mse, plus fk_weight * fk when
+// fk_weight > 0 (fk is not read otherwise; weights (1, 0) return mse itself).
+double train_total_loss(double mse_weight, double fk_weight, double mse, double fk);
+// From the slots' sums of e . e: the steps' fk terms weighted by their rows, and the
+// mean over the validation rows (NaN without any).
+void train_epoch_fk(const TrainEpoch &e, const double *sums, double *train_fk, double *val_fk);
+
 }  // namespace ikhip

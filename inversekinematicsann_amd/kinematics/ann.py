@@ -16,7 +16,9 @@ Training (ann.py:27-68): ANN.fit() runs the reference's recipe -- 67/33 split,
 StandardScalers fitted on the training part, Adam on MSE in batches of 32 with
 per-epoch shuffling, early stopping on val_loss -- with the forward, backward and
 Adam kernels of libikhip (ik_train.hip); the split, the scalers and the
-early-stopping loop are kinematics/train.py.  train_model() itself still raises.
+early-stopping loop are kinematics/train.py.  fit(..., fk_weight=W) adds W times the
+mean squared |FK(theta) - p| of the network's own angles to the loss
+(ik_ann_train_set_loss).  train_model() itself still raises.
 """
 from __future__ import annotations
 
@@ -131,7 +133,7 @@ class ANN:
 
     def fit(self, epochs, samples, features, *, batch_size=32, learning_rate=1e-5, patience=12,
             hidden=(12, 500, "tanh"), seed=0, test_size=0.33, split_seed=42,
-            verbose=False) -> dict:
+            verbose=False, mse_weight=1.0, fk_weight=0.0) -> dict:
         """Train the network on the GPU as the reference's train_model does
         (ann.py:27-68): train_test_split(test_size, random_state=split_seed),
         StandardScalers fitted on the training part (data cast to float32 after
@@ -147,9 +149,18 @@ class ANN:
         early stop; the last epoch's weights are installed only if no epoch's
         val_loss was ever finite).
 
+        mse_weight / fk_weight: the loss is mse_weight * mse + fk_weight * fk
+        (ik_ann_train_set_loss), fk the mean squared |FK(theta) - p| of the network's
+        own angles in the scalers' units undone.  With fk_weight > 0 the samples must
+        be positions (3 columns) and the features 4 joint angles, the chain is
+        self.dh_matrix when that is a 4 x 4 table (it becomes the context's robot),
+        else the context's robot, and 'loss' / 'val_loss', early stopping with them,
+        are the weighted totals.
+
         Returns {'loss': [...], 'val_loss': [...], 'best_epoch', 'stopped_epoch'}
-        (kinematics/train.py early_stopping_loop).  Afterwards predict() and
-        save_model() work as for a loaded model."""
+        (kinematics/train.py early_stopping_loop), with fk_weight > 0 also the
+        per-epoch lists 'fk' and 'val_fk'.  Afterwards predict() and save_model()
+        work as for a loaded model."""
         from . import train as T
         x = np.asarray(samples, dtype=np.float64)
         y = np.asarray(features, dtype=np.float64)
@@ -174,11 +185,26 @@ class ANN:
         ctx = _native.context()
         ctx.train_begin(model.weights, model.biases, acts,
                         max_batch=max(int(batch_size), min(4096, len(te))), lr=learning_rate)
+        with_fk = float(fk_weight) > 0.0
+        fks, val_fks = [], []
+
+        def run_epoch(e):
+            out = ctx.train_epoch(perm(len(tr)), int(batch_size))
+            if with_fk:
+                f, vf = ctx.train_fk()
+                fks.append(f)
+                val_fks.append(vf)
+            return out
         try:
+            if (float(mse_weight), float(fk_weight)) != (1.0, 0.0):
+                if with_fk and np.shape(self.dh_matrix) == (4, 4):
+                    ctx.set_robot(self.dh_matrix)
+                ctx.train_set_loss(mse_weight, fk_weight, xs.effective(), ys.effective())
             ctx.train_data(x_tr, y_tr, x_te, y_te)
             hist, best = T.early_stopping_loop(
-                epochs, patience, lambda e: ctx.train_epoch(perm(len(tr)), int(batch_size)),
-                lambda: ctx.train_get("weights"), verbose)
+                epochs, patience, run_epoch, lambda: ctx.train_get("weights"), verbose)
+            if with_fk:
+                hist["fk"], hist["val_fk"] = fks, val_fks
             if best is None and hist["loss"]:
                 best = ctx.train_get("weights")
         finally:

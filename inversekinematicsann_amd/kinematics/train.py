@@ -84,6 +84,47 @@ def early_stopping_loop(epochs: int, patience: int,
     return hist, best_w
 
 
+def fk_loss_reference(a, x, y, x_scaler, y_scaler, dh, mse_weight=1.0, fk_weight=0.0,
+                      act="linear"):
+    """The loss kernel's row arithmetic with the forward-kinematics term
+    (csrc/ik_train_fk_row.h, ik_ann_train_set_loss) in numpy float64, on
+    refine._chain / _consts.
+
+    a: the last layer's outputs (rows x 4), x: the scaled inputs (rows x 3), y: the
+    scaled labels (rows x 4); x_scaler / y_scaler: (mean, scale) pairs; dh: the 4 x 4
+    DH table; act: the last layer's activation.  With theta = a y_scale + y_mean,
+    p = x x_scale + x_mean and e = FK(wrap(theta)) - p (NaN when some |alpha_i| > 2 pi):
+
+        mse_sum = sum (a - y)^2            the batch's mse is mse_sum / (rows 4)
+        fk_sum  = sum e . e                the batch's fk  is fk_sum / rows
+        dZ[r][j] = (mse_weight 2 (a_j - y_j) / (rows 4)
+                    + fk_weight (2 / rows) (J_j . e) y_scale_j) act'(a_j)
+
+    Returns (mse_sum, fk_sum, dZ rows x 4 float64)."""
+    from .refine import _chain, _consts, wrap
+    a = np.asarray(a, np.float64).reshape(-1, 4)
+    x = np.asarray(x, np.float64).reshape(-1, 3)
+    y = np.asarray(y, np.float64).reshape(-1, 4)
+    xm, xs = (np.asarray(v, np.float64).reshape(3) for v in x_scaler)
+    ym, ys = (np.asarray(v, np.float64).reshape(4) for v in y_scaler)
+    rows = a.shape[0]
+    consts = _consts(dh, np.float64)
+    with np.errstate(all="ignore"):
+        th = wrap(a * ys + ym)
+        p = x * xs + xm
+        (fx, fy, fz), cols = _chain(consts, th)
+        e = np.stack([fx - p[:, 0], fy - p[:, 1], fz - p[:, 2]], axis=1)
+        if consts[4]:
+            e = np.full_like(e, np.nan)
+        je = np.stack([c[0] * e[:, 0] + c[1] * e[:, 1] + c[2] * e[:, 2] for c in cols], axis=1)
+        d = a - y
+        deriv = {"linear": np.ones_like(a), "tanh": 1.0 - a * a,
+                 "relu": (a > 0).astype(np.float64), "sigmoid": a * (1.0 - a)}[act]
+        dz = (float(mse_weight) * 2.0 / (rows * 4.0) * d
+              + float(fk_weight) * 2.0 / rows * je * ys) * deriv
+        return float((d * d).sum()), float((e * e).sum()), dz
+
+
 def epoch_permutations(seed: int):
     """Per-epoch shuffles: successive permutations of one default_rng(seed)."""
     rng = np.random.default_rng(seed)

@@ -41,6 +41,10 @@ def main(argv=None) -> int:
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--patience", type=int, default=12)
+    ap.add_argument("--mse-weight", type=float, default=1.0,
+                    help="weight of the mean squared error of the scaled angles")
+    ap.add_argument("--fk-weight", type=float, default=0.0,
+                    help="weight of the mean squared |FK(theta) - p| of the network's angles")
     args = ap.parse_args(argv)
     count, units = (int(v) for v in args.hidden.split(","))
 
@@ -57,17 +61,20 @@ def main(argv=None) -> int:
     t0 = time.perf_counter()
     hist = ann.fit(args.epochs, pts, ang, batch_size=args.batch, learning_rate=args.lr,
                    patience=args.patience, hidden=(count, units, "tanh"), seed=args.seed,
-                   verbose=True)
+                   verbose=True, mse_weight=args.mse_weight, fk_weight=args.fk_weight)
     secs = time.perf_counter() - t0
     path = ann.save_model(args.prefix)
     _, held = split_indices(len(pts))
     _, err, _ = ann.predict_with_fk_error(pts[held])
-    print(json.dumps({"model": path, "epochs_run": len(hist["loss"]),
-                      "best_epoch": hist["best_epoch"], "stopped_epoch": hist["stopped_epoch"],
-                      "loss": hist["loss"][-1], "val_loss": hist["val_loss"],
-                      "fit_seconds": round(secs, 3), "held_out": int(len(held)),
-                      "fk_err_mean_m": float(np.nanmean(err)),
-                      "fk_err_max_m": float(np.nanmax(err))}))
+    out = {"model": path, "epochs_run": len(hist["loss"]),
+           "best_epoch": hist["best_epoch"], "stopped_epoch": hist["stopped_epoch"],
+           "loss": hist["loss"][-1], "val_loss": hist["val_loss"],
+           "fit_seconds": round(secs, 3), "held_out": int(len(held)),
+           "fk_err_mean_m": float(np.nanmean(err)),
+           "fk_err_max_m": float(np.nanmax(err))}
+    if args.fk_weight > 0:
+        out["fk"], out["val_fk"] = hist["fk"][-1], hist["val_fk"]
+    print(json.dumps(out))
     return 0
 
 
