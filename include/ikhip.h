@@ -204,6 +204,54 @@ int ik_ann_solve_refined(ik_ctx *ctx, const double *pts, int64_t n, double tol, 
                          double damping, double *ang, int32_t *iters, double *fk_err,
                          double *seed_fk_err, int flags, ik_stats *stats);
 
+/* ---- Joint limits -------------------------------------------------------------
+ * The robot's joint limits, per joint an interval [lo, hi] of the wrapped angle.
+ * Joint i is free when lo[i] == -inf and hi[i] == +inf; otherwise it is limited and
+ * needs -pi <= lo[i] <= hi[i] <= pi, both finite (lo[i] == hi[i]: a fixed joint).
+ * lo == NULL and hi == NULL clear the limits; a fresh context has every joint free.
+ * They are host doubles of the context, indexed by joint like the DH columns:
+ * ik_set_robot does not touch them.  IK_E_BADARG, naming the joint (1..4) in
+ * ik_last_error and leaving the stored limits as they were: a NaN bound, lo > hi, a
+ * finite bound beyond +-pi, one infinite bound beside a finite one; also exactly one
+ * NULL array.
+ *
+ * Only ik_refine and ik_ann_solve_refined honour them.  ik_ann_solve, the FABRIK
+ * solves, ik_fk, ik_analytic_solve and the training calls ignore them: their
+ * results are bit-identical whether limits are set or not (ik_check_joint_limits
+ * shows what such a solve did with respect to them).
+ *
+ * The limited refine.  With every joint free the refine is the one above, bit for
+ * bit.  With at least one limited joint, per row:
+ *   theta_i = wrap(seed_i); limited i: theta_i = clip(theta_i)   (the seed, projected)
+ *   repeat:
+ *     e, err, J and the stop test as above (a NaN err stops at once)
+ *     L = {}                                    (the joints locked for this step)
+ *     solve: J' = J with the columns of L replaced by +0.0;
+ *            delta = J'^T (J' J'^T + damping^2 I)^-1 e, the sums and their order as above
+ *            N = {limited i not in L: (theta_i <= lo_i and delta_i < 0) or
+ *                                     (theta_i >= hi_i and delta_i > 0)}
+ *            N not empty: L = L + N, solve again       (at most 4 times: L only grows)
+ *     delta is scaled so that max |delta_i| <= 0.5 rad
+ *     free i: theta_i = wrap(theta_i + delta_i);  limited i: theta_i = clip(theta_i + delta_i)
+ * with clip(t) = (t < lo_i ? lo_i : t) > hi_i ? hi_i : that (a NaN stays NaN).  Every
+ * returned angle of a limited joint satisfies lo <= theta <= hi exactly.  Outputs,
+ * iters, fk_err, every field of stats and NaN rows are as for the free refine.  A
+ * goal that cannot be reached inside the limits ends at max_iter with finite angles
+ * inside them and counts in n_capped; such a row may have every useful joint locked
+ * and stand still.  A locked column adds only +0.0 terms, and clip(t) == t ==
+ * wrap(t) while |t| < pi: limits that never bind give the free refine's bits. */
+int ik_set_joint_limits(ik_ctx *ctx, const double *lo /*4*/, const double *hi /*4*/);
+int ik_get_joint_limits(ik_ctx *ctx, double *lo /*4*/, double *hi /*4*/);
+/* The rows of ang (n x 4 float64; host, or device with IK_F_DEVICE, then 16-byte
+ * aligned; IK_F_ASYNC allowed with it) that break the context's joint limits: row r
+ * does when for some limited joint i, with w = wrap(ang[r][i]), !(lo[i] <= w &&
+ * w <= hi[i]) -- a NaN therefore does.  stats: first_err the lowest such row (-1:
+ * none) with first_err_code IK_E_ANGLE_RANGE, n_capped their number, first_oob -1,
+ * all else 0.  With every joint free nothing violates.  IK_E_BADARG: n < 0, a NULL
+ * ang with n > 0, IK_F_ASYNC without IK_F_DEVICE. */
+int ik_check_joint_limits(ik_ctx *ctx, const double *ang /*n x 4*/, int64_t n, int flags,
+                          ik_stats *stats);
+
 /* ---- Analytic ----------------------------------------------------------------
  * Closed-form inverse kinematics with a chosen tool pitch and elbow branch, float64,
  * no iteration, for a context's robot that is a yaw joint followed by a planar

@@ -33,6 +33,7 @@ ACTS = {"linear": 0, "tanh": 1, "relu": 2, "sigmoid": 3}
 
 EXPORTED_SYMBOLS = ("ik_ctx_create", "ik_ctx_destroy", "ik_ctx_set_stream", "ik_ctx_get_stream",
                     "ik_last_error", "ik_version", "ik_set_robot", "ik_check_limits", "ik_fk", "ik_fk_chain",
+                    "ik_set_joint_limits", "ik_get_joint_limits", "ik_check_joint_limits",
                     "ik_fabrik_solve", "ik_fabrik_solve_fk", "ik_fabrik_calc", "ik_fabrik_reset_order", "ik_ann_load", "ik_ann_solve",
                     "ik_refine", "ik_ann_solve_refined", "ik_analytic_solve",
                     "ik_stats_fetch", "ik_ctx_set_timing", "ik_kernel_times",
@@ -120,6 +121,9 @@ def load_library(path: str = LIB_PATH):
         L.ik_version.restype = ctypes.c_char_p
         L.ik_set_robot.argtypes = [vp, dp, dp, dp]
         L.ik_check_limits.argtypes = [vp, dp, i64, ctypes.c_int, st]
+        L.ik_set_joint_limits.argtypes = [vp, dp, dp]
+        L.ik_get_joint_limits.argtypes = [vp, dp, dp]
+        L.ik_check_joint_limits.argtypes = [vp, dp, i64, ctypes.c_int, st]
         L.ik_fk.argtypes = [vp, dp, i64, dp, dp, ctypes.c_int, st]
         L.ik_fk_chain.argtypes = [vp, ctypes.c_int, dp, dp, i64, dp, dp, ctypes.c_int, st]
         L.ik_fabrik_solve.argtypes = [vp, dp, i64, ctypes.c_double, i32, dp, ip, dp, ctypes.c_int,
@@ -227,6 +231,7 @@ class Context:
                                  0.0, 2.0, 2.0, 2.0, np.pi / 2, 0.0, 0.0, 0.0]),
                        np.array([2.0, 2.0, 2.0, 2.0]), np.array([0.0, 6.0, -6.0, 6.0, -3.0, 6.0]))
         self.robot_uploads = 0
+        self._joint_limits = (np.full(4, -np.inf), np.full(4, np.inf))  # every joint free
 
     def close(self):
         if getattr(self, "handle", None):
@@ -264,7 +269,55 @@ class Context:
         self.robot_uploads += 1
         return True
 
+    def set_joint_limits(self, joint_limits) -> bool:
+        """The robot's joint limits, honoured by refine / ann_solve_refined only
+        (include/ikhip.h "Joint limits"): None clears them, else a pair (lo[4], hi[4])
+        with -inf / +inf for a free joint, or four entries, each (lo, hi) or None.
+        Compared with what the context holds: returns whether ik_set_joint_limits was
+        called.  A refused value (NativeError, IK_E_BADARG) leaves the limits."""
+        from .kinematics.refine import joint_limit_arrays
+        if joint_limits is None:
+            lo, hi = joint_limit_arrays(None)
+        else:
+            jl = list(joint_limits)
+            if len(jl) == 2 and all(e is not None and np.shape(e) == (4,) for e in jl):
+                lo, hi = (_host(e, np.float64).reshape(4).copy() for e in jl)  # the library judges
+            else:
+                lo, hi = joint_limit_arrays(jl)
+        # (bit patterns: -0.0 and 0.0 differ in what the kernel is handed)
+        if lo.tobytes() == self._joint_limits[0].tobytes() and \
+                hi.tobytes() == self._joint_limits[1].tobytes():
+            return False
+        if np.isneginf(lo).all() and np.isposinf(hi).all():
+            self._check(self.lib.ik_set_joint_limits(self.handle, None, None))
+        else:
+            self._check(self.lib.ik_set_joint_limits(self.handle, _ptr(lo), _ptr(hi)))
+        self._joint_limits = (lo, hi)
+        return True
+
+    def joint_limits(self):
+        """(lo, hi) as the library holds them (ik_get_joint_limits)."""
+        lo, hi = np.empty(4, np.float64), np.empty(4, np.float64)
+        self._check(self.lib.ik_get_joint_limits(self.handle, _ptr(lo), _ptr(hi)))
+        return lo, hi
+
     # -- solves ---------------------------------------------------------------
+    def check_joint_limits(self, ang) -> IkStats:
+        """ik_check_joint_limits of ang (n x 4; float32 angles are converted on the
+        host): first_err the lowest row breaking the joint limits, n_capped their
+        number."""
+        s = IkStats()
+        if _is_device(ang):
+            n = int(ang.shape[0])
+            a = self._dev(ang, "float64", (n, 4), "ang")
+            self._on_torch_stream(lambda: self._check(self.lib.ik_check_joint_limits(
+                self.handle, a, n, IK_F_DEVICE, ctypes.byref(s))))
+        else:
+            a = _host(ang, np.float64, 4)
+            self._check(self.lib.ik_check_joint_limits(self.handle, _ptr(a), a.shape[0], 0,
+                                                       ctypes.byref(s)))
+        return s
+
     def check_limits(self, pts) -> IkStats:
         s = IkStats()
         if _is_device(pts):

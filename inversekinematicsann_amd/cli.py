@@ -15,7 +15,10 @@ Extra flags: --tol / --max-iter (FABRIK, defaults 1e-3 / 100 as the
 reference's constructor), --device, and for --method ann --refine-tol FLOAT
 [--refine-iter INT, default 20]: the network's angles are polished on the GPU by
 the damped-least-squares refine (kinematics/refine.py) and written as float64;
---verbose then reports the network's and the polished FK error.
+--verbose then reports the network's and the polished FK error.  With --refine-tol,
+--joint-limits="lo:hi,lo:hi,,lo:hi" (radians, an empty field for a free joint) keeps
+the polished angles inside the robot's joint limits; --verbose adds how many points
+ended on a limit and how many did not converge.
 `--method analytic [--pitch FLOAT] [--elbow up|down] [--nearest-pitch]` (not in the
 reference) solves in closed form at a chosen tool pitch theta2 + theta3 + theta4 and
 elbow branch (kinematics/analytic.py); a fourth CSV column `pitch` gives one pitch per
@@ -73,6 +76,10 @@ def _parser():
     p.add_argument("--refine-tol", type=float, default=None,
                    help="ANN: polish the angles until |FK(theta) - p| <= this")
     p.add_argument("--refine-iter", type=int, default=20, help="ANN: refine step cap")
+    p.add_argument("--joint-limits", type=str, default=None,
+                   help='ANN with --refine-tol: "lo:hi,lo:hi,,lo:hi" in radians, one field per '
+                        'joint, an empty field for a free joint (write --joint-limits=... when '
+                        'the first bound is negative)')
     p.add_argument("--pitch", type=float, default=None,
                    help="analytic: tool pitch theta2 + theta3 + theta4 of every point (radians)")
     p.add_argument("--elbow", choices=["up", "down"], default=None,
@@ -123,6 +130,24 @@ def _verbose(points, joint_angles):
           f"over {len(err)} points")
 
 
+def _joint_limits(text, parser):
+    """--joint-limits "lo:hi,lo:hi,,lo:hi": four entries, (lo, hi) or None."""
+    fields = text.split(",")
+    if len(fields) != 4:
+        parser.error(f"--joint-limits takes 4 comma-separated fields, got {len(fields)}")
+    out = []
+    for i, f in enumerate(fields):
+        if not f.strip():
+            out.append(None)
+            continue
+        try:
+            lo, hi = (float(v) for v in f.split(":"))
+        except ValueError:
+            parser.error(f"--joint-limits: joint {i + 1}: expected lo:hi, got {f!r}")
+        out.append((lo, hi))
+    return out
+
+
 def _ikine(args, parser):
     from .robot.robot import OutOfRobotReachException
     from .robot.robot import SixDOFRobot as Robot
@@ -137,6 +162,16 @@ def _ikine(args, parser):
         parser.error("the following arguments are required: --model")
     if args.refine_tol is not None and args.method != "ann":
         parser.error("--refine-tol is only valid with --method ann")
+    joint_limits = None
+    if args.joint_limits is not None:
+        if args.method != "ann" or args.refine_tol is None:
+            parser.error("--joint-limits is only valid with --method ann --refine-tol")
+        joint_limits = _joint_limits(args.joint_limits, parser)
+        from .kinematics.refine import joint_limit_arrays
+        try:
+            joint_limit_arrays(joint_limits)
+        except ValueError as e:
+            parser.error(f"--joint-limits: {e}")
     if args.method != "analytic":
         for flag, given in (("--pitch", args.pitch is not None), ("--elbow", args.elbow is not None),
                             ("--nearest-pitch", args.nearest_pitch)):
@@ -158,7 +193,7 @@ def _ikine(args, parser):
         refine = (None if args.refine_tol is None
                   else {"tol": args.refine_tol, "max_iter": args.refine_iter})
         ik = AnnInverseKinematics(dh, Robot.links_lengths, Robot.effector_workspace_limits,
-                                  refine=refine)
+                                  refine=refine, joint_limits=joint_limits)
         ik.load_model(args.model)
     elif args.method == "fabrik":
         ik = FabrikInverseKinematics(dh, Robot.links_lengths, Robot.effector_workspace_limits,
@@ -176,6 +211,12 @@ def _ikine(args, parser):
                   f"refined to tol {args.refine_tol:g} in max {int(it.max())} steps "
                   f"(mean {it.mean():.3g}), {ik.last_stats.n_capped} of {len(it)} points not "
                   "converged")
+            if joint_limits is not None:
+                lo, hi = ik.joint_limits
+                ang = np.asarray(joint_angles, np.float64)
+                at = int(((ang == lo) | (ang == hi)).any(axis=1).sum())
+                print(f"joint limits: {at} of {len(it)} points at a limit, "
+                      f"{ik.last_stats.n_capped} not converged")
         if args.method == "analytic":
             print(f"analytic: max |FK(theta) - p| = {np.nanmax(ik.last_fk_err):.6g} (in the solve's "
                   f"launch), {ik.last_stats.n_capped} of {len(points)} pitches moved")

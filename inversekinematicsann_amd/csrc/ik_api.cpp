@@ -549,6 +549,51 @@ int ik_check_limits(ik_ctx *c, const double *pts, int64_t n, int flags, ik_stats
   return finish(c, flags, stats);
 }
 
+// ---- joint limits (honoured by the refine: ik_refine.hip) -----------------------
+int ik_set_joint_limits(ik_ctx *c, const double *lo, const double *hi) {
+  if (!c) return fail(IK_E_BADARG, "ik_set_joint_limits: NULL context");
+  if (!lo != !hi)
+    return fail(IK_E_BADARG, "ik_set_joint_limits: lo and hi must both be given or both be NULL");
+  JointLimits jl = {{-HUGE_VAL, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL},
+                    {HUGE_VAL, HUGE_VAL, HUGE_VAL, HUGE_VAL}, 0u};
+  for (int i = 0; lo && i < 4; ++i) {
+    const std::string who = "ik_set_joint_limits: joint " + std::to_string(i + 1) + ": ";
+    if (std::isnan(lo[i]) || std::isnan(hi[i])) return fail(IK_E_BADARG, who + "a bound is NaN");
+    if (lo[i] == -HUGE_VAL && hi[i] == HUGE_VAL) continue;  // free
+    if (std::isinf(lo[i]) != std::isinf(hi[i]))
+      return fail(IK_E_BADARG, who + "one bound is infinite and the other finite");
+    if (lo[i] > hi[i]) return fail(IK_E_BADARG, who + "lo > hi");
+    if (lo[i] < -kPi || hi[i] > kPi)
+      return fail(IK_E_BADARG, who + "a bound lies outside [-pi, pi]");
+    jl.lo[i] = lo[i];
+    jl.hi[i] = hi[i];
+    jl.mask |= 1u << i;
+  }
+  c->jlim = jl;
+  return IK_OK;
+}
+
+int ik_get_joint_limits(ik_ctx *c, double *lo, double *hi) {
+  if (!c || !lo || !hi) return fail(IK_E_BADARG, "ik_get_joint_limits: bad args");
+  std::memcpy(lo, c->jlim.lo, sizeof(c->jlim.lo));
+  std::memcpy(hi, c->jlim.hi, sizeof(c->jlim.hi));
+  return IK_OK;
+}
+
+int ik_check_joint_limits(ik_ctx *c, const double *ang, int64_t n, int flags, ik_stats *stats) {
+  if (!c || n < 0 || (n > 0 && !ang)) return fail(IK_E_BADARG, "ik_check_joint_limits: bad args");
+  int rc = check_flags("ik_check_joint_limits", flags, ang);
+  if (rc || (rc = set_dev(c))) return rc;
+  KtScope kts(c);
+  Stage st(c, flags);
+  const int r_ang = st.in(ang, (size_t)n * 32);
+  if ((rc = st.reserve())) return rc;
+  launch_reset_stats(c->d_stats, c->stream);
+  launch_check_joint_limits(c->jlim, st.at<const double>(r_ang), n, c->d_stats, c->stream);
+  IK_HIP(hipGetLastError());
+  return finish(c, flags, stats);
+}
+
 int ik_fk(ik_ctx *c, const double *ang, int64_t n, double *xyz, double *mats, int flags,
           ik_stats *stats) {
   if (!c || n < 0 || (n > 0 && (!ang || !xyz))) return fail(IK_E_BADARG, "ik_fk: bad args");
@@ -849,7 +894,7 @@ int ik_refine(ik_ctx *c, const double *pts, const double *seed, int64_t n, doubl
   launch_reset_stats(c->d_stats, c->stream);
   launch_refine(c->rconst, st.at<const double>(r_pts), st.at<const double>(r_seed), n, tol,
                 max_iter, damping, st.at<double>(r_ang), st.at<int32_t>(r_it),
-                st.at<double>(r_fe), !(flags & IK_F_NO_LIMITS), c->d_stats, c->stream);
+                st.at<double>(r_fe), !(flags & IK_F_NO_LIMITS), c->jlim, c->d_stats, c->stream);
   IK_HIP(hipGetLastError());
   if ((rc = st.flush())) return rc;
   return finish(c, flags, stats);
@@ -878,7 +923,8 @@ int ik_ann_solve_refined(ik_ctx *c, const double *pts, int64_t n, double tol, in
   // the call's stats are the refined result's
   launch_reset_stats(c->d_stats, c->stream);
   launch_refine_f32(c->rconst, dp, dseed, n, tol, max_iter, damping, st.at<double>(r_ang),
-                    st.at<int32_t>(r_it), st.at<double>(r_fe), limits, c->d_stats, c->stream);
+                    st.at<int32_t>(r_it), st.at<double>(r_fe), limits, c->jlim, c->d_stats,
+                    c->stream);
   IK_HIP(hipGetLastError());
   if ((rc = st.flush())) return rc;
   return finish(c, flags, stats);

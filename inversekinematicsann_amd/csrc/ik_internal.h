@@ -105,6 +105,10 @@ struct ik_ctx {
   void *scratch = nullptr;
   size_t scratch_bytes = 0;
   ikhip::RobotDev robot;
+  // the robot's joint limits (ik_set_joint_limits): host state, handed to the refine
+  // kernels by value; ik_set_robot leaves them.  A fresh context: every joint free.
+  ikhip::JointLimits jlim = {{-HUGE_VAL, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL},
+                             {HUGE_VAL, HUGE_VAL, HUGE_VAL, HUGE_VAL}, 0u};
   bool ann_loaded = false;
   ikhip::AnnModelDev ann;
   void *ann_buf = nullptr;

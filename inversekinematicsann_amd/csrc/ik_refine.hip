@@ -9,10 +9,17 @@
 // the wrap to [-pi, pi].  kinematics/refine.py restates it operation for operation;
 // the only difference is sincos_fk against libm's sin / cos (<= 1.2e-16).
 //
+// The 3 x 3 solve is ik_refine_step.h's, which a host program compiles too.  With
+// joint limits (ik_set_joint_limits) a second instantiation of the same kernel runs:
+// the same chain, the step from that header's active-set loop (wave-uniform, the
+// locked columns selected to +0.0), a limited joint clipped to [lo, hi] where a free
+// one is wrapped.  Limits that never bind give the free instantiation's bits.
+//
 // The wave iterates until no lane is active; a finished lane keeps its angles (the
 // update is a select) and recomputes the same error.  HBM per row: 24 B goal +
 // 32 / 16 B seed in, 32 B angles (+ 4 B count + 8 B error) out.
 #include "ik_common.h"
+#include "ik_refine_step.h"
 
 namespace ikhip {
 
@@ -24,12 +31,16 @@ __device__ __forceinline__ double wrap_pi(double t) {
   return t - kTwoPi * __builtin_rint(t / kTwoPi);
 }
 
-template <typename SeedT>
+// kLimited: the robot's joint limits jl hold (wave-uniform, by value); a limited
+// joint's angle is pulled into [lo, hi] where a free one is wrapped, and the step
+// comes from the active-set loop.  Without, jl is not read.
+template <typename SeedT, bool kLimited>
 __global__ __launch_bounds__(256) void refine_kernel(const RobotConstDev *rc, const double *pts,
                                                      const SeedT *seed, int64_t n, double tol,
                                                      int max_iter, double lam2, double *ang,
                                                      int32_t *iters, double *fk_err,
-                                                     int check_limits, DevStats *S) {
+                                                     int check_limits, DevStats *S,
+                                                     JointLimits jl) {
   const RcConst k = (RcConst)rc;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool valid = i < n;
@@ -42,6 +53,12 @@ __global__ __launch_bounds__(256) void refine_kernel(const RobotConstDev *rc, co
     t1 = wrap_pi((double)seed[4 * i + 1]);
     t2 = wrap_pi((double)seed[4 * i + 2]);
     t3 = wrap_pi((double)seed[4 * i + 3]);
+    if constexpr (kLimited) {  // the projection of the seed
+      t0 = (jl.mask & 1u) ? refine_project(t0, jl.lo[0], jl.hi[0]) : t0;
+      t1 = (jl.mask & 2u) ? refine_project(t1, jl.lo[1], jl.hi[1]) : t1;
+      t2 = (jl.mask & 4u) ? refine_project(t2, jl.lo[2], jl.hi[2]) : t2;
+      t3 = (jl.mask & 8u) ? refine_project(t3, jl.lo[3], jl.hi[3]) : t3;
+    }
     if (check_limits) {
       const double lim[6] = {k->lim[0], k->lim[1], k->lim[2], k->lim[3], k->lim[4], k->lim[5]};
       if (outside(lim, px, py, pz)) atomicMin(&S->first_oob, (unsigned long long)i);
@@ -160,29 +177,17 @@ __global__ __launch_bounds__(256) void refine_kernel(const RobotConstDev *rc, co
     }
     if (!__any(active)) break;
 
-    // A = J J^T + lambda^2 I (rows x, y, z; column 1 has no z part)
-    const double A00 = j0x * j0x + j1x * j1x + j2x * j2x + j3x * j3x + lam2;
-    const double A10 = j0y * j0x + j1y * j1x + j2y * j2x + j3y * j3x;
-    const double A11 = j0y * j0y + j1y * j1y + j2y * j2y + j3y * j3y + lam2;
-    const double A20 = j1z * j1x + j2z * j2x + j3z * j3x;
-    const double A21 = j1z * j1y + j2z * j2y + j3z * j3y;
-    const double A22 = j1z * j1z + j2z * j2z + j3z * j3z + lam2;
-    // LDL^T, no pivoting (A is SPD)
-    const double l10 = A10 / A00, l20 = A20 / A00;
-    const double D1 = A11 - l10 * A10;
-    const double u21 = A21 - l20 * A10;
-    const double l21 = u21 / D1;
-    const double D2 = A22 - l20 * A20 - l21 * u21;
-    const double y1 = ey - l10 * ex;
-    const double y2 = ez - l20 * ex - l21 * y1;
-    const double q2 = y2 / D2;
-    const double q1 = y1 / D1 - l21 * q2;
-    const double q0 = ex / A00 - l10 * q1 - l20 * q2;
-    // delta = J^T q
-    double e0 = j0x * q0 + j0y * q1;
-    double e1 = j1x * q0 + j1y * q1 + j1z * q2;
-    double e2 = j2x * q0 + j2y * q1 + j2z * q2;
-    double e3 = j3x * q0 + j3y * q1 + j3z * q2;
+    // delta = J'^T (J' J'^T + lambda^2 I)^-1 e (ik_refine_step.h): every column, or
+    // under joint limits without those the active-set loop locks
+    const RefineJ J = {j0x, j0y, j1x, j1y, j1z, j2x, j2y, j2z, j3x, j3y, j3z};
+    double dl[4];
+    if constexpr (kLimited) {
+      const double tt[4] = {t0, t1, t2, t3};
+      refine_step(J, ex, ey, ez, lam2, tt, jl, dl, nullptr);
+    } else {
+      refine_solve(J, ex, ey, ez, lam2, 0u, dl);
+    }
+    double e0 = dl[0], e1 = dl[1], e2 = dl[2], e3 = dl[3];
     const double m = fmax(fmax(fabs(e0), fabs(e1)), fmax(fabs(e2), fabs(e3)));
     if (m > kRefineClamp) {
       const double sc = kRefineClamp / m;
@@ -192,10 +197,17 @@ __global__ __launch_bounds__(256) void refine_kernel(const RobotConstDev *rc, co
       e3 = e3 * sc;
     }
     if (active) {
-      t0 = wrap_pi(t0 + e0);
-      t1 = wrap_pi(t1 + e1);
-      t2 = wrap_pi(t2 + e2);
-      t3 = wrap_pi(t3 + e3);
+      if constexpr (kLimited) {
+        t0 = (jl.mask & 1u) ? refine_project(t0 + e0, jl.lo[0], jl.hi[0]) : wrap_pi(t0 + e0);
+        t1 = (jl.mask & 2u) ? refine_project(t1 + e1, jl.lo[1], jl.hi[1]) : wrap_pi(t1 + e1);
+        t2 = (jl.mask & 4u) ? refine_project(t2 + e2, jl.lo[2], jl.hi[2]) : wrap_pi(t2 + e2);
+        t3 = (jl.mask & 8u) ? refine_project(t3 + e3, jl.lo[3], jl.hi[3]) : wrap_pi(t3 + e3);
+      } else {
+        t0 = wrap_pi(t0 + e0);
+        t1 = wrap_pi(t1 + e1);
+        t2 = wrap_pi(t2 + e2);
+        t3 = wrap_pi(t3 + e3);
+      }
       ++it;
     }
   }
@@ -217,28 +229,66 @@ __global__ __launch_bounds__(256) void refine_kernel(const RobotConstDev *rc, co
 template <typename SeedT>
 static void launch_refine_t(const RobotConstDev *rc, const double *pts, const SeedT *seed,
                             int64_t n, double tol, int max_iter, double damping, double *ang,
-                            int32_t *iters, double *fk_err, bool check_limits, DevStats *S,
-                            hipStream_t st) {
+                            int32_t *iters, double *fk_err, bool check_limits,
+                            const JointLimits &jl, DevStats *S, hipStream_t st) {
   if (n <= 0) return;
   const unsigned grid = (unsigned)((n + 255) / 256);
-  kt_begin("refine_kernel", st);
-  IK_LAUNCH(refine_kernel<SeedT>, dim3(grid), dim3(256), 0, st, rc, pts, seed, n, tol, max_iter,
-            damping * damping, ang, iters, fk_err, check_limits ? 1 : 0, S);
+  // every joint free: the kernel without the limits' code
+  if (jl.mask) {
+    kt_begin("refine_limited_kernel", st);
+    IK_LAUNCH((refine_kernel<SeedT, true>), dim3(grid), dim3(256), 0, st, rc, pts, seed, n, tol,
+              max_iter, damping * damping, ang, iters, fk_err, check_limits ? 1 : 0, S, jl);
+  } else {
+    kt_begin("refine_kernel", st);
+    IK_LAUNCH((refine_kernel<SeedT, false>), dim3(grid), dim3(256), 0, st, rc, pts, seed, n, tol,
+              max_iter, damping * damping, ang, iters, fk_err, check_limits ? 1 : 0, S, jl);
+  }
   kt_end(st);
 }
 
 void launch_refine(const RobotConstDev *rc, const double *pts, const double *seed, int64_t n,
                    double tol, int max_iter, double damping, double *ang, int32_t *iters,
-                   double *fk_err, bool check_limits, DevStats *S, hipStream_t st) {
-  launch_refine_t(rc, pts, seed, n, tol, max_iter, damping, ang, iters, fk_err, check_limits, S,
-                  st);
+                   double *fk_err, bool check_limits, const JointLimits &jl, DevStats *S,
+                   hipStream_t st) {
+  launch_refine_t(rc, pts, seed, n, tol, max_iter, damping, ang, iters, fk_err, check_limits, jl,
+                  S, st);
 }
 
 void launch_refine_f32(const RobotConstDev *rc, const double *pts, const float *seed, int64_t n,
                        double tol, int max_iter, double damping, double *ang, int32_t *iters,
-                       double *fk_err, bool check_limits, DevStats *S, hipStream_t st) {
-  launch_refine_t(rc, pts, seed, n, tol, max_iter, damping, ang, iters, fk_err, check_limits, S,
-                  st);
+                       double *fk_err, bool check_limits, const JointLimits &jl, DevStats *S,
+                       hipStream_t st) {
+  launch_refine_t(rc, pts, seed, n, tol, max_iter, damping, ang, iters, fk_err, check_limits, jl,
+                  S, st);
+}
+
+// ik_check_joint_limits: a row violates when a limited joint's wrapped angle is not
+// inside [lo, hi] (a NaN is not).  The lowest violating row goes to first_err with
+// IK_E_ANGLE_RANGE, the rows' count to n_capped (one atomic per wave).
+__global__ __launch_bounds__(256) void check_joint_limits_kernel(JointLimits jl, const double *ang,
+                                                                 int64_t n, DevStats *S) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  if (i < n) {
+    const double2 *a = reinterpret_cast<const double2 *>(ang + 4 * i);
+    const double2 a01 = a[0], a23 = a[1];
+    const double w[4] = {wrap_pi(a01.x), wrap_pi(a01.y), wrap_pi(a23.x), wrap_pi(a23.y)};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      bad = bad | (((jl.mask >> j) & 1u) && !(jl.lo[j] <= w[j] && w[j] <= jl.hi[j]));
+    if (bad) record_error(S, i, IK_E_ANGLE_RANGE);
+  }
+  const unsigned long long c = (unsigned long long)__popcll(__ballot(bad));
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(&S->n_capped[blockIdx.x % kStatShards], c);
+}
+
+void launch_check_joint_limits(const JointLimits &jl, const double *ang, int64_t n, DevStats *S,
+                               hipStream_t st) {
+  if (n <= 0 || !jl.mask) return;  // every joint free: nothing violates
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  kt_begin("check_joint_limits_kernel", st);
+  IK_LAUNCH(check_joint_limits_kernel, dim3(grid), dim3(256), 0, st, jl, ang, n, S);
+  kt_end(st);
 }
 
 }  // namespace ikhip

@@ -125,6 +125,9 @@ class ANN:
         self.x_data_skaler = None
         self.y_data_skaler = None
         self._uploaded_to = None
+        # the joint limits predict_refined honours (AnnInverseKinematics sets them):
+        # None, or what Context.set_joint_limits takes
+        self.joint_limits = None
 
     def train_model(self, epochs, samples, features):
         raise NotImplementedError("ANN training (kinematics/ann.py:27-68) is not part of the "
@@ -234,6 +237,8 @@ class ANN:
                          xm, xs, ym, ys)
             self._uploaded_to = ctx
             ctx._ann_owner = self
+        # this object's joint limits or none: another object's never leak into its calls
+        ctx.set_joint_limits(self.joint_limits)
         return ctx
 
     def predict(self, position):

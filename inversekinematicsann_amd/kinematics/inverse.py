@@ -28,6 +28,7 @@ from ..robot.robot import OutOfRobotReachException
 from .analytic import ELBOWS
 from .ann import ANN, as_features as as_ann_points
 from .forward import ForwardKinematics
+from .refine import joint_limit_arrays
 from .fabrik import Fabrik
 
 _ERR_EXC = {
@@ -77,11 +78,13 @@ class InverseKinematics(ABC):
         """The process context holding this object's robot: uploaded when it
         differs from what the context holds (Context.set_robot compares), so
         objects with different robots can interleave and repeated calls of one
-        object upload nothing."""
+        object upload nothing.  Its joint limits likewise: this object's, or none
+        (only AnnInverseKinematics with refine has any)."""
         ctx = _native.context()
         ctx.set_robot(np.asarray(self.dh_matrix, np.float64),
                       np.asarray(self.joints_distances, np.float64),
                       limits_array(self.workspace_limits))
+        ctx.set_joint_limits(getattr(self, "joint_limits", None))
         return ctx
 
     def _raise_out_of_reach(self, dest_points, idx):
@@ -136,14 +139,28 @@ class FabrikInverseKinematics(InverseKinematics):
 class AnnInverseKinematics(InverseKinematics):
     """Reaching inverse kinematics using the ANN method (inverse.py:142-155)."""
 
-    def __init__(self, dh_matrix, joints_distances, workspace_limits, refine=None):
+    def __init__(self, dh_matrix, joints_distances, workspace_limits, refine=None,
+                 joint_limits=None):
         """refine: None (the reference's behaviour: the network's float32 angles),
         True, or a dict with any of tol / max_iter / damping: ikine then returns the
         angles polished by the library's damped-least-squares refine (float64;
         defaults 1e-6 / 20 / 1e-3, kinematics/refine.py) and sets last_iterations,
-        last_fk_err and last_seed_fk_err."""
+        last_fk_err and last_seed_fk_err.
+
+        joint_limits: four entries, each (lo, hi) in [-pi, pi] or None for a free
+        joint; the refine then keeps every limited angle inside its interval
+        (include/ikhip.h "Joint limits").  Only with refine: the bare network cannot
+        honour them (ValueError)."""
         super().__init__(dh_matrix, joints_distances, workspace_limits)
         self.ann = ANN(workspace_limits, dh_matrix)
+        if joint_limits is not None:
+            if refine is None or refine is False:
+                raise ValueError("joint_limits need refine: the network alone cannot honour "
+                                 "them")
+            if len(list(joint_limits)) != 4:
+                raise ValueError("joint_limits: four entries, each (lo, hi) or None")
+            joint_limits = joint_limit_arrays(list(joint_limits))
+        self.joint_limits = self.ann.joint_limits = joint_limits
         if refine is None or refine is False:
             self.refine = None
         else:

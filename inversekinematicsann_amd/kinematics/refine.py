@@ -19,6 +19,13 @@ B_i = Tz(d_i) Tx(a_i) Rx(alpha_i)), the same sums in the same order, no fused
 multiply-add -- so in float64 it differs from the kernel only by the kernel's
 sin / cos (within 1.2e-16 of libm's).
 
+With joint limits (ik_set_joint_limits; refine_reference(joint_limits=...)) a limited
+joint's angle is pulled into [lo, hi] where a free one is wrapped -- the seed too --
+and d comes from an active-set loop: a limited joint on a bound whose d_i points
+out of the interval has its column of J replaced by +0.0 and the system is solved
+again, until no new joint locks (csrc/ik_refine_step.h, restated by _solve and
+_limited_step).  joint_limit_violations is the twin of ik_check_joint_limits.
+
 Known limits: a goal outside reach, or on the line of a fully stretched seed
 (fixed damping does not leave that singular direction), ends at max_iter with
 finite angles and err > tol.
@@ -89,10 +96,118 @@ def jacobian(dh, ang):
     return np.stack([np.stack(col, axis=1) for col in J], axis=2)
 
 
+def joint_limit_arrays(joint_limits):
+    """(lo, hi), two float64 arrays of 4 with -inf / +inf for a free joint, from None
+    (every joint free), a pair (lo[4], hi[4]) or four entries, each (lo, hi) or None.
+    The library's refusals (ik_set_joint_limits) as ValueError naming the joint."""
+    lo, hi = np.full(4, -np.inf), np.full(4, np.inf)
+    if joint_limits is None:
+        return lo, hi
+    jl = list(joint_limits)
+    if len(jl) == 2 and all(e is not None and np.shape(e) == (4,) for e in jl):
+        lo, hi = np.array(jl[0], np.float64), np.array(jl[1], np.float64)
+    elif len(jl) == 4:
+        for i, e in enumerate(jl):
+            if e is not None:
+                lo[i], hi[i] = (float(v) for v in e)
+    else:
+        raise ValueError("joint_limits: four entries, each (lo, hi) or None, or a pair "
+                         "(lo[4], hi[4])")
+    for i in range(4):
+        who = f"joint_limits: joint {i + 1}: "
+        if np.isnan(lo[i]) or np.isnan(hi[i]):
+            raise ValueError(who + "a bound is NaN")
+        if lo[i] == -np.inf and hi[i] == np.inf:
+            continue
+        if np.isinf(lo[i]) != np.isinf(hi[i]):
+            raise ValueError(who + "one bound is infinite and the other finite")
+        if lo[i] > hi[i]:
+            raise ValueError(who + "lo > hi")
+        if lo[i] < -np.pi or hi[i] > np.pi:
+            raise ValueError(who + "a bound lies outside [-pi, pi]")
+    return lo, hi
+
+
+def joint_limit_violations(ang, joint_limits):
+    """The numpy twin of ik_check_joint_limits: one bool per row of ang (n x 4), true
+    when some limited joint's wrapped angle w has !(lo <= w <= hi) (a NaN has)."""
+    lo, hi = joint_limit_arrays(joint_limits)
+    limited = ~((lo == -np.inf) & (hi == np.inf))
+    w = wrap(np.asarray(ang, np.float64).reshape(-1, 4))
+    with np.errstate(invalid="ignore"):
+        return (~((lo <= w) & (w <= hi)) & limited).any(axis=1)
+
+
+def _project(t, lo, hi):
+    """ik_refine_step.h refine_project: t pulled into [lo, hi], a NaN stays NaN."""
+    t = np.where(t < lo, lo, t)
+    return np.where(t > hi, hi, t)
+
+
+def _solve(J, e, lam2, lock):
+    """ik_refine_step.h refine_solve: delta (4 arrays) = J'^T (J' J'^T + lam2 I)^-1 e
+    with the columns lock[:, i] of J replaced by +0.0 (lock None: none)."""
+    j0, j1, j2, j3 = J
+    if lock is not None:
+        zero = np.zeros_like(e[0])
+        j0, j1, j2, j3 = ([np.where(lock[:, i], zero, c) for c in col]
+                          for i, col in enumerate(J))
+    ex, ey, ez = e
+    A00 = j0[0] * j0[0] + j1[0] * j1[0] + j2[0] * j2[0] + j3[0] * j3[0] + lam2
+    A10 = j0[1] * j0[0] + j1[1] * j1[0] + j2[1] * j2[0] + j3[1] * j3[0]
+    A11 = j0[1] * j0[1] + j1[1] * j1[1] + j2[1] * j2[1] + j3[1] * j3[1] + lam2
+    A20 = j1[2] * j1[0] + j2[2] * j2[0] + j3[2] * j3[0]
+    A21 = j1[2] * j1[1] + j2[2] * j2[1] + j3[2] * j3[1]
+    A22 = j1[2] * j1[2] + j2[2] * j2[2] + j3[2] * j3[2] + lam2
+    l10, l20 = A10 / A00, A20 / A00
+    D1 = A11 - l10 * A10
+    u21 = A21 - l20 * A10
+    l21 = u21 / D1
+    D2 = A22 - l20 * A20 - l21 * u21
+    y1 = ey - l10 * ex
+    y2 = ez - l20 * ex - l21 * y1
+    q2 = y2 / D2
+    q1 = y1 / D1 - l21 * q2
+    q0 = ex / A00 - l10 * q1 - l20 * q2
+    e0 = j0[0] * q0 + j0[1] * q1
+    e1 = j1[0] * q0 + j1[1] * q1 + j1[2] * q2
+    e2 = j2[0] * q0 + j2[1] * q1 + j2[2] * q2
+    e3 = j3[0] * q0 + j3[1] * q1 + j3[2] * q2
+    return e0, e1, e2, e3
+
+
+def _limited_step(J, e, lam2, th, lo, hi, limited):
+    """ik_refine_step.h refine_step on every row: (delta, lock n x 4 bool, re-solves
+    per row).  As in the kernel's wave, all rows solve again while any row has a new
+    lock; a row with nothing new gets the same values."""
+    n = th.shape[0]
+    lock = np.zeros((n, 4), bool)
+    resolves = np.zeros(n, np.int32)
+    while True:
+        d = _solve(J, e, lam2, lock)
+        dd = np.stack(d, axis=1)
+        new = (((th <= lo) & (dd < 0)) | ((th >= hi) & (dd > 0))) & limited & ~lock
+        lock = lock | new
+        grew = new.any(axis=1)
+        resolves = resolves + grew.astype(np.int32)
+        if not grew.any():
+            return d, lock, resolves
+
+
 def refine_reference(pts, seed, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER,
-                     damping=DEFAULT_DAMPING, dh=None, dtype=np.float64):
+                     damping=DEFAULT_DAMPING, dh=None, dtype=np.float64, joint_limits=None,
+                     trace=None):
     """The refine of every (pts[i], seed[i]); returns (theta n x 4, iters n int32,
-    err n) in dtype (np.float64 or np.longdouble)."""
+    err n) in dtype (np.float64 or np.longdouble).
+
+    joint_limits: None, or what joint_limit_arrays takes ((lo, hi) with -inf / +inf
+    for a free joint).  With at least one limited joint the step is the library's
+    limited refine (include/ikhip.h "Joint limits"), restated operation for operation;
+    with none the code path is the free one.
+
+    trace: a list that receives one dict per step of the limited refine -- the rows
+    that took it (rows), J (11 columns: j0x j0y j1x .. j3z), e, theta before the step,
+    delta before the 0.5 rad scaling, the lock mask (bits) and the re-solves."""
     if dh is None:
         from ..robot.robot import SixDOFRobot
         dh = SixDOFRobot.dh_matrix
@@ -100,6 +215,11 @@ def refine_reference(pts, seed, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER,
     consts = _consts(dh, dtype)
     p = np.asarray(pts, dtype).reshape(-1, 3)
     th = wrap(np.asarray(seed, dtype).reshape(-1, 4), dtype)
+    lo64, hi64 = joint_limit_arrays(joint_limits)
+    limited = ~((lo64 == -np.inf) & (hi64 == np.inf))
+    lo, hi = lo64.astype(dtype), hi64.astype(dtype)
+    if limited.any():
+        th = np.where(limited, _project(th, lo, hi), th)
     n = p.shape[0]
     tol = dtype(tol)
     lam2 = dtype(np.float64(damping) * np.float64(damping))
@@ -109,7 +229,7 @@ def refine_reference(pts, seed, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER,
     active = np.ones(n, bool)
     with np.errstate(all="ignore"):
         while n:
-            (x, y, z), (j0, j1, j2, j3) = _chain(consts, th)
+            (x, y, z), J = _chain(consts, th)
             ex, ey, ez = p[:, 0] - x, p[:, 1] - y, p[:, 2] - z
             en = np.sqrt(ex * ex + ey * ey + ez * ez)
             if consts[4]:
@@ -118,30 +238,28 @@ def refine_reference(pts, seed, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER,
             active = active & ~(~(err > tol) | (it == max_iter))
             if not active.any():
                 break
-            A00 = j0[0] * j0[0] + j1[0] * j1[0] + j2[0] * j2[0] + j3[0] * j3[0] + lam2
-            A10 = j0[1] * j0[0] + j1[1] * j1[0] + j2[1] * j2[0] + j3[1] * j3[0]
-            A11 = j0[1] * j0[1] + j1[1] * j1[1] + j2[1] * j2[1] + j3[1] * j3[1] + lam2
-            A20 = j1[2] * j1[0] + j2[2] * j2[0] + j3[2] * j3[0]
-            A21 = j1[2] * j1[1] + j2[2] * j2[1] + j3[2] * j3[1]
-            A22 = j1[2] * j1[2] + j2[2] * j2[2] + j3[2] * j3[2] + lam2
-            l10, l20 = A10 / A00, A20 / A00
-            D1 = A11 - l10 * A10
-            u21 = A21 - l20 * A10
-            l21 = u21 / D1
-            D2 = A22 - l20 * A20 - l21 * u21
-            y1 = ey - l10 * ex
-            y2 = ez - l20 * ex - l21 * y1
-            q2 = y2 / D2
-            q1 = y1 / D1 - l21 * q2
-            q0 = ex / A00 - l10 * q1 - l20 * q2
-            e0 = j0[0] * q0 + j0[1] * q1
-            e1 = j1[0] * q0 + j1[1] * q1 + j1[2] * q2
-            e2 = j2[0] * q0 + j2[1] * q1 + j2[2] * q2
-            e3 = j3[0] * q0 + j3[1] * q1 + j3[2] * q2
+            if limited.any():
+                (e0, e1, e2, e3), lock, resolves = _limited_step(J, (ex, ey, ez), lam2, th, lo,
+                                                                 hi, limited)
+                if trace is not None:
+                    rows = np.flatnonzero(active)
+                    cols = [J[0][0], J[0][1]] + [c for col in J[1:] for c in col]
+                    trace.append({
+                        "rows": rows, "J": np.stack(cols, axis=1)[rows],
+                        "e": np.stack([ex, ey, ez], axis=1)[rows], "theta": th[rows],
+                        "delta": np.stack([e0, e1, e2, e3], axis=1)[rows],
+                        "lock": (lock[rows] << np.arange(4)).sum(axis=1),
+                        "resolves": resolves[rows]})
+            else:
+                e0, e1, e2, e3 = _solve(J, (ex, ey, ez), lam2, None)
             m = np.fmax(np.fmax(np.abs(e0), np.abs(e1)), np.fmax(np.abs(e2), np.abs(e3)))
             big = m > clamp
             sc = np.where(big, clamp / np.where(big, m, 1), 1)
             d = np.stack([np.where(big, e * sc, e) for e in (e0, e1, e2, e3)], axis=1)
-            th = np.where(active[:, None], wrap(th + d, dtype), th)
+            if limited.any():
+                new = np.where(limited, _project(th + d, lo, hi), wrap(th + d, dtype))
+            else:
+                new = wrap(th + d, dtype)
+            th = np.where(active[:, None], new, th)
             it = it + active.astype(np.int32)
     return th, it, err
