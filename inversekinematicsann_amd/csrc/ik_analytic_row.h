@@ -13,15 +13,8 @@
 // s3 = sqrt(1 - c3^2) loses about eps a2 a3 / W.
 #pragma once
 
-#include <math.h>
-
 #include "ik_analytic_plan.h"
-
-#if defined(__HIPCC__)
-#define IK_ROW_FN __host__ __device__ inline
-#else
-#define IK_ROW_FN inline
-#endif
+#include "ik_row.h"
 
 namespace ikhip {
 
@@ -30,12 +23,6 @@ struct AnalyticRow {
   double phi;             // the pitch used (NaN when the row failed)
   bool fail, moved;
 };
-
-// theta - 2 pi rint(theta / 2 pi), as ik_refine wraps
-IK_ROW_FN double analytic_wrap(double t) {
-  const double two_pi = 2 * 3.141592653589793;
-  return t - two_pi * rint(t / two_pi);
-}
 
 struct AnalyticWrist {
   double wr, wh, m, q;
@@ -70,7 +57,7 @@ IK_ROW_FN AnalyticRow analytic_row(const AnalyticRobot &R, double x, double y, d
     const double sa = R.a2 + R.a3, da = fabs(R.a2 - R.a3), den = 2 * R.a4 * rho;
     const double cmin = (rho2 + R.a4 * R.a4 - sa * sa) / den;
     const double cmax = (rho2 + R.a4 * R.a4 - da * da) / den;
-    const double dl = analytic_wrap(phi - gam);
+    const double dl = wrap_pi(phi - gam);
     // (dl == dl: a NaN or infinite pitch has no nearest one)
     const bool any = cmin <= 1.0 && cmax >= -1.0 && rho > 0.0 && dl == dl;
     if (any) {
@@ -89,8 +76,8 @@ IK_ROW_FN AnalyticRow analytic_row(const AnalyticRobot &R, double x, double y, d
   const double s3 = b * sqrt(w.m * w.q), c3 = (w.q - w.m) / 2;
   o.t3 = b * 2 * atan2(sqrt(w.m), sqrt(w.q));
   const double t2 = atan2(w.wh, w.wr) - atan2(R.a3 * s3, R.a2 + R.a3 * c3);
-  o.t4 = analytic_wrap(phi - t2 - o.t3);
-  o.t2 = analytic_wrap(t2);
+  o.t4 = wrap_pi(phi - t2 - o.t3);
+  o.t2 = wrap_pi(t2);
   o.phi = phi;
   if (o.fail) o.t1 = o.t2 = o.t3 = o.t4 = o.phi = __builtin_nan("");
   return o;

@@ -2,14 +2,13 @@
 // ik_ann_solve_refined; DESIGN.md section 3 "Refine").
 //
 // One goal per lane, fp64 VALU, everything in registers.  Per step: the FK chain
-// of fk_error_cs (ik_common.h) applied right to left to a vector, with the four
-// Jacobian columns riding along -- d Rz(t_i) v / dt_i = (-y', x', 0) of the rotated
-// (x', y'), then only the rotations to its left -- A = J J^T + lambda^2 I (3 x 3,
-// six entries), LDL^T without pivoting, delta = J^T A^-1 e, the 0.5 rad clamp and
-// the wrap to [-pi, pi].  kinematics/refine.py restates it operation for operation;
-// the only difference is sincos_fk against libm's sin / cos (<= 1.2e-16).
+// with its four Jacobian columns (ik_chain_jac.h, shared with the training loss's FK
+// term), A = J J^T + lambda^2 I (3 x 3, six entries), LDL^T without pivoting,
+// delta = J^T A^-1 e, the 0.5 rad clamp and the wrap to [-pi, pi] (ik_row.h).
+// kinematics/refine.py restates it operation for operation; the only difference is
+// sincos_fk against libm's sin / cos (<= 1.2e-16).
 //
-// The 3 x 3 solve is ik_refine_step.h's, which a host program compiles too.  With
+// The chain and the 3 x 3 solve (ik_refine_step.h) are compiled by host programs too.  With
 // joint limits (ik_set_joint_limits) a second instantiation of the same kernel runs:
 // the same chain, the step from that header's active-set loop (wave-uniform, the
 // locked columns selected to +0.0), a limited joint clipped to [lo, hi] where a free
@@ -23,13 +22,7 @@
 
 namespace ikhip {
 
-constexpr double kTwoPi = 2 * kPi;
 constexpr double kRefineClamp = 0.5;  // largest |delta_i| of one step, radians
-
-// theta - 2 pi rint(theta / 2 pi): in [-pi, pi] (exact for |theta| <= 8 pi)
-__device__ __forceinline__ double wrap_pi(double t) {
-  return t - kTwoPi * __builtin_rint(t / kTwoPi);
-}
 
 // kLimited: the robot's joint limits jl hold (wave-uniform, by value); a limited
 // joint's angle is pulled into [lo, hi] where a free one is wrapped, and the step
@@ -64,112 +57,23 @@ __global__ __launch_bounds__(256) void refine_kernel(const RobotConstDev *rc, co
       if (outside(lim, px, py, pz)) atomicMin(&S->first_oob, (unsigned long long)i);
     }
   }
-  // B_i = Tz(d_i) Tx(a_i) Rx(alpha_i): jc[i] = {a_i, d_i, cos alpha_i, sin alpha_i}
-  const double a1 = k->jc[0], d1 = k->jc[1], ca1 = k->jc[2], sa1 = k->jc[3];
-  const double a2 = k->jc[4], d2 = k->jc[5], ca2 = k->jc[6], sa2 = k->jc[7];
-  const double a3 = k->jc[8], d3_ = k->jc[9], ca3 = k->jc[10], sa3 = k->jc[11];
-  const double a4 = k->jc[12], d4 = k->jc[13];
+  double jc[14];  // fk_trip_consts' per-joint constants, wave-uniform
+#pragma unroll
+  for (int j = 0; j < 14; ++j) jc[j] = k->jc[j];
   const bool alpha_ok = !k->alpha_bad;  // some |alpha_i| > 2 pi: FK raises, the error is NaN
 
   bool active = valid;
   int it = 0;
   double err = 0.0;
   for (;;) {
-    double s0, c0, s1, c1, s2, c2, s3, c3;
-    sincos_fk(t0, &s0, &c0);
-    sincos_fk(t1, &s1, &c1);
-    sincos_fk(t2, &s2, &c2);
-    sincos_fk(t3, &s3, &c3);
-    // ---- joint 4: v = B4 e4 = (a4, 0, d4); Rz(t4)
-    double x = a4, y = 0.0, z = d4;
-    double xr = c3 * x - s3 * y, yr = s3 * x + c3 * y;
-    double j3x = -yr, j3y = xr, j3z = 0.0;  // column 4
-    x = xr;
-    y = yr;
-    // B3, then its rotation on the open column
-    double yb = ca3 * y - sa3 * z, zb = sa3 * y + ca3 * z + d3_;
-    x = x + a3;
-    y = yb;
-    z = zb;
-    double wy = ca3 * j3y - sa3 * j3z, wz = sa3 * j3y + ca3 * j3z;
-    j3y = wy;
-    j3z = wz;
-    // ---- joint 3: Rz(t3)
-    xr = c2 * x - s2 * y;
-    yr = s2 * x + c2 * y;
-    double j2x = -yr, j2y = xr, j2z = 0.0;  // column 3
-    x = xr;
-    y = yr;
-    double wx = c2 * j3x - s2 * j3y;
-    wy = s2 * j3x + c2 * j3y;
-    j3x = wx;
-    j3y = wy;
-    // B2
-    yb = ca2 * y - sa2 * z;
-    zb = sa2 * y + ca2 * z + d2;
-    x = x + a2;
-    y = yb;
-    z = zb;
-    wy = ca2 * j3y - sa2 * j3z;
-    wz = sa2 * j3y + ca2 * j3z;
-    j3y = wy;
-    j3z = wz;
-    wy = ca2 * j2y - sa2 * j2z;
-    wz = sa2 * j2y + ca2 * j2z;
-    j2y = wy;
-    j2z = wz;
-    // ---- joint 2: Rz(t2)
-    xr = c1 * x - s1 * y;
-    yr = s1 * x + c1 * y;
-    double j1x = -yr, j1y = xr, j1z = 0.0;  // column 2
-    x = xr;
-    y = yr;
-    wx = c1 * j3x - s1 * j3y;
-    wy = s1 * j3x + c1 * j3y;
-    j3x = wx;
-    j3y = wy;
-    wx = c1 * j2x - s1 * j2y;
-    wy = s1 * j2x + c1 * j2y;
-    j2x = wx;
-    j2y = wy;
-    // B1
-    yb = ca1 * y - sa1 * z;
-    zb = sa1 * y + ca1 * z + d1;
-    x = x + a1;
-    y = yb;
-    z = zb;
-    wy = ca1 * j3y - sa1 * j3z;
-    wz = sa1 * j3y + ca1 * j3z;
-    j3y = wy;
-    j3z = wz;
-    wy = ca1 * j2y - sa1 * j2z;
-    wz = sa1 * j2y + ca1 * j2z;
-    j2y = wy;
-    j2z = wz;
-    wy = ca1 * j1y - sa1 * j1z;
-    wz = sa1 * j1y + ca1 * j1z;
-    j1y = wy;
-    j1z = wz;
-    // ---- joint 1: Rz(t1)
-    xr = c0 * x - s0 * y;
-    yr = s0 * x + c0 * y;
-    const double j0x = -yr, j0y = xr;  // column 1 (its z is 0)
-    x = xr;
-    y = yr;
-    wx = c0 * j3x - s0 * j3y;
-    wy = s0 * j3x + c0 * j3y;
-    j3x = wx;
-    j3y = wy;
-    wx = c0 * j2x - s0 * j2y;
-    wy = s0 * j2x + c0 * j2y;
-    j2x = wx;
-    j2y = wy;
-    wx = c0 * j1x - s0 * j1y;
-    wy = s0 * j1x + c0 * j1y;
-    j1x = wx;
-    j1y = wy;
+    double s[4], c[4];
+    sincos_fk(t0, &s[0], &c[0]);
+    sincos_fk(t1, &s[1], &c[1]);
+    sincos_fk(t2, &s[2], &c[2]);
+    sincos_fk(t3, &s[3], &c[3]);
+    const ChainJac f = fk_chain_jac(jc, s, c);  // the effector and dFK / dtheta
 
-    const double ex = px - x, ey = py - y, ez = pz - z;
+    const double ex = px - f.x, ey = py - f.y, ez = pz - f.z;
     const double en = sqrt(ex * ex + ey * ey + ez * ez);
     if (active) {
       err = alpha_ok ? en : __builtin_nan("");
@@ -179,13 +83,12 @@ __global__ __launch_bounds__(256) void refine_kernel(const RobotConstDev *rc, co
 
     // delta = J'^T (J' J'^T + lambda^2 I)^-1 e (ik_refine_step.h): every column, or
     // under joint limits without those the active-set loop locks
-    const RefineJ J = {j0x, j0y, j1x, j1y, j1z, j2x, j2y, j2z, j3x, j3y, j3z};
     double dl[4];
     if constexpr (kLimited) {
       const double tt[4] = {t0, t1, t2, t3};
-      refine_step(J, ex, ey, ez, lam2, tt, jl, dl, nullptr);
+      refine_step(f.J, ex, ey, ez, lam2, tt, jl, dl, nullptr);
     } else {
-      refine_solve(J, ex, ey, ez, lam2, 0u, dl);
+      refine_solve(f.J, ex, ey, ez, lam2, 0u, dl);
     }
     double e0 = dl[0], e1 = dl[1], e2 = dl[2], e3 = dl[3];
     const double m = fmax(fmax(fabs(e0), fabs(e1)), fmax(fabs(e2), fabs(e3)));

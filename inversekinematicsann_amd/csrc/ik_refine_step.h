@@ -3,7 +3,8 @@
 // limits" state the arithmetic; kinematics/refine.py restates it in numpy).
 // Compiled by the kernel (ik_refine.hip) and by a plain host compiler
 // (tests/host/refine_limits_check.cpp): every operation is the same IEEE operation
-// in the same order (-ffp-contract=off), so both give the same bits.
+// in the same order (-ffp-contract=off), so both give the same bits.  J (RefineJ)
+// comes from the chain of ik_chain_jac.h, which is held to the same contract.
 //
 // refine_solve: A = J' J'^T + lambda^2 I (3 x 3, six entries), LDL^T without
 // pivoting, delta = J'^T A^-1 e, where J' is J with the columns of the lock mask
@@ -18,15 +19,7 @@
 // lane with nothing new solves the same system again and gets the same values.
 #pragma once
 
-#include <math.h>
-
-#ifndef IK_ROW_FN
-#if defined(__HIPCC__)
-#define IK_ROW_FN __host__ __device__ inline
-#else
-#define IK_ROW_FN inline
-#endif
-#endif
+#include "ik_chain_jac.h"
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define IK_REFINE_ANY(p) __any(p)
@@ -42,14 +35,6 @@ namespace ikhip {
 struct JointLimits {
   double lo[4], hi[4];
   unsigned mask;
-};
-
-// The Jacobian's columns (column 1 has no z part).
-struct RefineJ {
-  double j0x, j0y;
-  double j1x, j1y, j1z;
-  double j2x, j2y, j2z;
-  double j3x, j3y, j3z;
 };
 
 // t pulled into [lo, hi]; a NaN stays NaN.

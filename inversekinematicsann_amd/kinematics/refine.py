@@ -14,7 +14,8 @@ For one goal p and seed theta_0 (4 revolute joints of a DH table):
         theta <- wrap(theta + d);  it <- it + 1
 
 refine_reference follows the kernel operation for operation -- the same chain
-(the effector as Rz(t1) B1 Rz(t2) B2 Rz(t3) B3 Rz(t4) B4 e4 applied right to left,
+(csrc/ik_chain_jac.h, restated by _chain_cs: the effector as
+Rz(t1) B1 Rz(t2) B2 Rz(t3) B3 Rz(t4) B4 e4 applied right to left,
 B_i = Tz(d_i) Tx(a_i) Rx(alpha_i)), the same sums in the same order, no fused
 multiply-add -- so in float64 it differs from the kernel only by the kernel's
 sin / cos (within 1.2e-16 of libm's).
@@ -57,13 +58,19 @@ def wrap(theta, dtype=np.float64):
 
 def _chain(consts, th):
     """The effector (x, y, z) and the Jacobian's columns [(jx, jy, jz)] * 4 of the
-    angle rows th (n x 4): ik_refine.hip's sequence."""
+    angle rows th (n x 4): _chain_cs on numpy's sines and cosines."""
+    return _chain_cs(consts, np.sin(th), np.cos(th))
+
+
+def _chain_cs(consts, s, c):
+    """The same from the angles' sines and cosines (n x 4 each): the sequence of
+    csrc/ik_chain_jac.h fk_chain_jac, which the refine kernel and the training loss's
+    FK term both call."""
     a, d, ca, sa, _ = consts
-    s, c = np.sin(th), np.cos(th)
-    n = th.shape[0]
-    x = np.full(n, a[3], th.dtype)
-    y = np.zeros(n, th.dtype)
-    z = np.full(n, d[3], th.dtype)
+    n, dtype = s.shape[0], s.dtype
+    x = np.full(n, a[3], dtype)
+    y = np.zeros(n, dtype)
+    z = np.full(n, d[3], dtype)
     cols = []  # open columns, the latest joint first
     for i in (3, 2, 1, 0):
         ci, si = c[:, i], s[:, i]
@@ -73,7 +80,7 @@ def _chain(consts, th):
             wx = ci * w[0] - si * w[1]
             wy = si * w[0] + ci * w[1]
             w[0], w[1] = wx, wy
-        cols.append([-yr, xr, np.zeros(n, th.dtype)])  # d Rz(t_i) v / dt_i
+        cols.append([-yr, xr, np.zeros(n, dtype)])  # d Rz(t_i) v / dt_i
         x, y = xr, yr
         if i > 0:  # B_i (1-based): Rx(alpha), then the translations (a, 0, d)
             b = i - 1
