@@ -8,8 +8,11 @@
 // its index; the lanes around it are not affected (the infeasible / nearest path
 // is one short branch whose both sides leave the row finite or NaN by design).
 // HBM per row: 24 B goal (+ 8 B pitch) in, 32 B angles (+ 8 B pitch + 8 B error) out.
+#include "ik_analytic.h"
 #include "ik_analytic_row.h"
-#include "ik_common.h"
+#include "ik_fk_chain.h"
+#include "ik_launch.h"
+#include "ik_stats.h"
 
 namespace ikhip {
 

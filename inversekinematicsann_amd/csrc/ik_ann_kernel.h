@@ -30,7 +30,11 @@
 #include <type_traits>
 
 #include "ik_act.h"
-#include "ik_common.h"
+#include "ik_ann.h"
+#include "ik_ann_pack.h"
+#include "ik_fk_chain.h"
+#include "ik_launch.h"
+#include "ik_stats.h"
 
 namespace ikhip {
 // The device code is compiled twice: for widths <= 512 (ik_ann.hip and ik_ann_x.hip,

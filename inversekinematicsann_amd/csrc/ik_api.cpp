@@ -16,9 +16,18 @@
 #include <string>
 #include <vector>
 
+#include "ik_analytic.h"
 #include "ik_analytic_plan.h"
+#include "ik_ann.h"
+#include "ik_ann_pack.h"
+#include "ik_fabrik.h"
 #include "ik_fabrik_prior.h"
+#include "ik_fk.h"
+#include "ik_fk_chain.h"
 #include "ik_internal.h"
+#include "ik_launch.h"
+#include "ik_refine.h"
+#include "ik_types.h"
 
 using namespace ikhip;
 

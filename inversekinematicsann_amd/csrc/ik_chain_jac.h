@@ -1,6 +1,6 @@
 // ik_chain_jac.h -- the forward-kinematics chain with its Jacobian, the one copy the
 // refine (ik_refine.hip) and the training loss's FK term (ik_train_fk_row.h) share:
-// the effector Rz(t1) B1 Rz(t2) B2 Rz(t3) B3 Rz(t4) B4 e4 of fk_error_cs (ik_common.h),
+// the effector Rz(t1) B1 Rz(t2) B2 Rz(t3) B3 Rz(t4) B4 e4 of fk_error_cs (ik_fk_chain.h),
 // B_i = Tz(d_i) Tx(a_i) Rx(alpha_i), applied right to left to a vector, with the four
 // Jacobian columns riding along -- d Rz(t_i) v / dt_i = (-y', x', 0) of the rotated
 // (x', y'), then only the rotations to its left.  Compiled by the kernels, which take

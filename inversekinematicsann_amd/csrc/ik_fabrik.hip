@@ -4,7 +4,10 @@
 //   FabrikInverseKinematics.ikine   kinematics/inverse.py:115-139
 //   Fabrik.calculate / __backward / __forward   kinematics/fabrik.py:19-67
 //   __get_angles                    kinematics/inverse.py:54-112
-// with the same operation order, so iteration counts are bit-exact.
+// with the same operation order, so iteration counts are bit-exact.  This unit
+// holds the iteration kernels and their launch; the iteration's arithmetic is
+// ik_fabrik_step.h, the angles step's ik_fabrik_angles.h, the work order's
+// kernels ik_fabrik_order.hip and Fabrik.calculate on its own ik_fabrik_calc.hip.
 //
 // Two pipelines (DESIGN.md "FABRIK"):
 //  * fused (default): classify + scatter (the hard-first work order, 6 bytes
@@ -19,268 +22,17 @@
 #include <algorithm>
 #include <cmath>
 
-#include "ik_common.h"
+#include "ik_arith.h"
+#include "ik_fabrik.h"
+#include "ik_fabrik_angles.h"
+#include "ik_fabrik_args.h"
+#include "ik_fabrik_plan.h"
 #include "ik_fabrik_step.h"
+#include "ik_fk_chain.h"
+#include "ik_launch.h"
+#include "ik_stats.h"
 
 namespace ikhip {
-
-// kinematics/inverse.py:54-112 __get_angles; J = FABRIK joints B, C, D, E.
-__device__ __forceinline__ void get_angles(const d3 J[4], double th[4], int &st) {
-  const d3 A = {0.0, 0.0, 0.0};
-  const d3 B = J[0], C = J[1], D = J[2], E = J[3];
-  th[0] = atan2(E.y, E.x);
-  double ab = dist3(A, B), bc = dist3(B, C), cd = dist3(C, D), de = dist3(D, E);
-  double ac = dist3(A, C);
-  double num = (sq(ab) + sq(bc)) - sq(ac);
-  double den = 2 * ab * bc;
-  double a2 = py_acos(py_round8(py_div(num, den, st)), st);
-  th[1] = (C.x * D.x < 0) ? ((3 * kPi / 2) - a2) : -(kPi / 2 - a2);
-  double bd = dist3(B, D);
-  num = (sq(bc) + sq(cd)) - sq(bd);
-  den = 2 * bc * cd;
-  double a3 = py_acos(py_round8(py_div(num, den, st)), st);
-  th[2] = -(kPi - a3);
-  double ce = dist3(C, E);
-  num = (sq(cd) + sq(de)) - sq(ce);
-  den = 2 * cd * de;
-  double a4 = py_acos(py_round8(py_div(num, den, st)), st);
-  d3 m = point_between(C, E, dist3(C, E) / 2, st);
-  double da = dist3(B, m);
-  double db = dist3(B, D);
-  th[3] = (db > da) ? -(kPi - a4) : (kPi - a4);
-}
-
-// ---- the angles step through cheaper sequences ------------
-// Everything __get_angles compares or rounds -- the distances, the law-of-
-// cosines quotients, round(., 8), the C.x D.x and |B - D| > |B - m| tests -- must
-// keep the reference's bits (a different round(., 8) moves an angle by up to
-// 1e-4 near a straight joint).  sqrt_core / div_core give those bits on their
-// domains (ik_common.h).  Only the final math.acos / math.atan2 values leave
-// the kernel, and those need not be glibc's last bit (ocml's never were): the
-// angles are held to 1e-9 of the oracle (the north star's tolerance is 1e-5).
-// acos_fast / atan2_fast: polynomials fitted against mpmath (asin on [0, 1/2],
-// degree 11 in u^2, <= 2.1 ulp; atan on [0, tan(pi/8)], degree 10, <= 1 ulp), the
-// usual reductions, pi split in two parts.  ~40 VALU instructions each against
-// ~100 (ocml acos) and ~114 (ocml atan2).
-constexpr double kPio2Hi = 0x1.921fb54442d18p0, kPio2Lo = 0x1.1a62633145c07p-54;
-constexpr double kPio4Hi = 0x1.921fb54442d18p-1, kPio4Lo = 0x1.1a62633145c07p-55;
-constexpr double kPiHi = 0x1.921fb54442d18p1, kPiLo = 0x1.1a62633145c07p-53;
-
-// asin(u) for u in [0, 1/2]: u + u z P(z), z = u^2 (z passed in)
-__device__ __forceinline__ double asin_small(double u, double z) {
-  double p = 0x1.c4e4e17088d7fp-6;
-  p = __builtin_fma(p, z, -0x1.478579af5a664p-7);
-  p = __builtin_fma(p, z, 0x1.fe14951c32a4cp-7);
-  p = __builtin_fma(p, z, 0x1.0524bf7ebc431p-7);
-  p = __builtin_fma(p, z, 0x1.83eb350c10662p-7);
-  p = __builtin_fma(p, z, 0x1.c89fb23c062d2p-7);
-  p = __builtin_fma(p, z, 0x1.1c5717f04e8d6p-6);
-  p = __builtin_fma(p, z, 0x1.6e8b4bd3059d9p-6);
-  p = __builtin_fma(p, z, 0x1.f1c71e76e5bd8p-6);
-  p = __builtin_fma(p, z, 0x1.6db6db6aaeb82p-5);
-  p = __builtin_fma(p, z, 0x1.3333333335124p-4);
-  p = __builtin_fma(p, z, 0x1.555555555555fp-3);
-  return __builtin_fma(u * z, p, u);
-}
-
-// atan(t) for |t| <= tan(pi/8): t + t s P(s), s = t^2
-__device__ __forceinline__ double atan_small(double t) {
-  const double s = t * t;
-  double p = -0x1.f318cc05bca37p-7;
-  p = __builtin_fma(p, s, 0x1.2487560b8b924p-5);
-  p = __builtin_fma(p, s, -0x1.959b5ed0b32b2p-5);
-  p = __builtin_fma(p, s, 0x1.dd91ab8788317p-5);
-  p = __builtin_fma(p, s, -0x1.10d3fc8f710cbp-4);
-  p = __builtin_fma(p, s, 0x1.3b0f4916f8726p-4);
-  p = __builtin_fma(p, s, -0x1.745ce3b26915fp-4);
-  p = __builtin_fma(p, s, 0x1.c71c705fa87fap-4);
-  p = __builtin_fma(p, s, -0x1.24924921fc848p-3);
-  p = __builtin_fma(p, s, 0x1.99999999958a3p-3);
-  p = __builtin_fma(p, s, -0x1.5555555555541p-2);
-  return __builtin_fma(t * s, p, t);
-}
-
-// math.acos on [-1, 1] (NaN outside, and for NaN): |x| <= 1/2 as pi/2 -+ asin|x|,
-// else 2 asin(sqrt((1 - |x|) / 2)) (x > 0) or pi minus it; 1 - |x| is exact there.
-__device__ __forceinline__ double acos_fast(double x) {
-  const double ax = fabs(x);
-  const bool small = ax <= 0.5;
-  const double zl = (1.0 - ax) * 0.5;  // 0 or >= 2^-54: sqrt_core's domain or 0
-  const double z = small ? x * x : zl;
-  const double u = small ? ax : (zl > 0.0 ? sqrt_core(zl) : 0.0);
-  const double p = asin_small(u, z);
-  const double r_small = x >= 0.0 ? kPio2Hi - (p - kPio2Lo) : kPio2Hi + (p + kPio2Lo);
-  const double r_large = x > 0.0 ? 2.0 * p : kPiHi - (2.0 * p - kPiLo);
-  const double r = small ? r_small : r_large;
-  return ax <= 1.0 ? r : __builtin_nan("");
-}
-
-// math.atan2 where both |x| and |y| are in [2^-100, 2^100] (div_core's domain);
-// the caller sends zeros, non-finite and extreme values to the library's atan2.
-__device__ __forceinline__ double atan2_fast(double y, double x) {
-  const double ax = fabs(x), ay = fabs(y);
-  const bool swap = ay > ax;
-  const double r = div_core(swap ? ax : ay, swap ? ay : ax);  // [0, 1]
-  const bool red = r > 0x1.a827999fcef32p-2;  // tan(pi/8): atan r = pi/4 + atan((r-1)/(r+1))
-  const double t = red ? div_core(r - 1.0, r + 1.0) : r;
-  double a = atan_small(t);
-  a = red ? kPio4Hi + (a + kPio4Lo) : a;
-  a = swap ? kPio2Hi - (a - kPio2Lo) : a;
-  a = x < 0.0 ? kPiHi - (a - kPiLo) : a;
-  return copysign(a, y);
-}
-
-__device__ __forceinline__ bool in_div_domain(double v) {
-  const double a = fabs(v);
-  return a >= 0x1p-100 && a <= 0x1p100;
-}
-
-// dist3 through sqrt_core (same bits where dom stays below kCoreDom)
-__device__ __forceinline__ double dist3c(d3 a, d3 b, uint32_t &dom) {
-  const double x = dist3_sq(a, b);
-  dom = max(dom, sqrt_core_dom(x));
-  return sqrt_core(x);
-}
-
-// round(v, 8) (py_round8) with the final k / 1e8 through div_core
-__device__ __forceinline__ double py_round8_core(double v, bool &ok) {
-  const double s = 1e8;
-  const double p = v * s;
-  if (!isfinite(p)) return v;
-  const double e = fma(v, s, -p);
-  const double fl = floor(p);
-  double k;
-  if (p - fl == 0.5) {
-    k = (e > 0) ? fl + 1.0 : ((e < 0) ? fl : rint(p));
-  } else {
-    k = rint(p);
-  }
-  ok = ok && (k == 0.0 || in_div_domain(k));
-  double r = div_core(k, s);
-  if (r == 0.0) r = copysign(0.0, v);
-  return r;
-}
-
-// sqrt(1 - v^2) = sin(acos(v)) for |v| <= 1 (the FK round trip's sines): 1 - v^2
-// in one rounding (fma), its root from the hardware estimate and one coupled
-// Newton step -- a few ulps, far inside the round trip's 1e-12 (its value is only
-// reported, never compared: tests/test_gpu_parity.py
-// ::test_fabrik_fk_err_equals_standalone_fk).
-__device__ __forceinline__ double sin_of_acos(double v) {
-  const double t = __builtin_fma(-v, v, 1.0);
-  const double y = __builtin_amdgcn_rsq(t);
-  const double h = 0.5 * y, g = t * y;
-  const double e = __builtin_fma(-h, g, 0.5);
-  return t > 0.0 ? __builtin_fma(g, e, g) : 0.0;
-}
-
-// __get_angles (inverse.py:54-112) through the core sequences; returns false
-// (and the caller runs get_angles) when some radicand or quotient leaves their
-// domains -- coincident joints, a zero divisor, non-finite joints -- or the
-// effector's x or y is zero or extreme (atan2's special cases).
-// cs / sn: the angles' cosines and sines for the FK round trip (cli.py:54-61),
-// from the values the angles come from instead of sin / cos of the angles:
-// theta_1 = atan2(E.y, E.x) gives (E.x, E.y) / |(E.x, E.y)|, and every other angle
-// is +-(k pi / 2 -+ acos(v)) of a law-of-cosines value v, so its cosine and sine
-// are +-v and +-sqrt(1 - v^2).  They differ from sin / cos of the rounded angles
-// by a few ulps (the rounding of the angles themselves), not 4 x 40 instructions.
-__device__ __forceinline__ bool get_angles_core(const d3 J[4], double th[4], int &st,
-                                                double cs[4], double sn[4]) {
-  const d3 A = {0.0, 0.0, 0.0};
-  const d3 B = J[0], C = J[1], D = J[2], E = J[3];
-  uint32_t dom = 0;
-  bool ok = in_div_domain(E.x) && in_div_domain(E.y);
-  const double ab = dist3c(A, B, dom), bc = dist3c(B, C, dom), cd = dist3c(C, D, dom),
-               de = dist3c(D, E, dom);
-  const double ac = dist3c(A, C, dom);
-  auto quot = [&](double num, double den) {
-    ok = ok && (num == 0.0 || in_div_domain(num)) && in_div_domain(den);
-    return div_core(num, den);
-  };
-  auto acos_py = [&](double v) {
-    if (v > 1.0 || v < -1.0) set_err(st, IK_E_DOMAIN);
-    return acos_fast(v);
-  };
-  double num = (sq(ab) + sq(bc)) - sq(ac);
-  double den = 2 * ab * bc;
-  const double v2 = py_round8_core(quot(num, den), ok);
-  const double a2 = acos_py(v2);
-  const bool up = C.x * D.x < 0;
-  th[1] = up ? ((3 * kPi / 2) - a2) : -(kPi / 2 - a2);
-  const double w2 = sin_of_acos(v2);
-  cs[1] = up ? -w2 : w2;  // cos(3 pi / 2 - a) = -sin a, cos(a - pi / 2) = sin a
-  sn[1] = -v2;            // sin of either is -cos a
-  const double bd = dist3c(B, D, dom);
-  num = (sq(bc) + sq(cd)) - sq(bd);
-  den = 2 * bc * cd;
-  const double v3 = py_round8_core(quot(num, den), ok);
-  const double a3 = acos_py(v3);
-  th[2] = -(kPi - a3);
-  cs[2] = -v3;  // a - pi
-  sn[2] = -sin_of_acos(v3);
-  const double ce = dist3c(C, E, dom);
-  num = (sq(cd) + sq(de)) - sq(ce);
-  den = 2 * cd * de;
-  const double v4 = py_round8_core(quot(num, den), ok);
-  const double a4 = acos_py(v4);
-  // get_point_between(C, E, |C - E| / 2): |C - E| is ce again (the radicand squares
-  // E - C = -(C - E) exactly) and (ce / 2) / ce is exactly 0.5 for a ce in the domain
-  const d3 m = {C.x + (0.5 * (E.x - C.x)), C.y + (0.5 * (E.y - C.y)), C.z + (0.5 * (E.z - C.z))};
-  const double da = dist3c(B, m, dom);
-  th[3] = (bd > da) ? -(kPi - a4) : (kPi - a4);  // db = |B - D| = bd
-  cs[3] = -v4;  // a - pi or pi - a
-  const double w4 = sin_of_acos(v4);
-  sn[3] = (bd > da) ? -w4 : w4;
-  // th[0] = atan2_fast(E.y, E.x): by the caller, after the fallback pass; its
-  // cosine and sine from E (E.x, E.y in the division domain: t is normal)
-  {
-    const double t = E.x * E.x + E.y * E.y;
-    const double y = __builtin_amdgcn_rsq(t);
-    const double h = 0.5 * y, g = t * y;
-    const double e = __builtin_fma(-h, g, 0.5);
-    const double yi = __builtin_fma(y, e, y);
-    cs[0] = E.x * yi;
-    sn[0] = E.y * yi;
-  }
-  return ok && dom < kCoreDom;
-}
-
-// The per-robot constants (RobotConstDev).  jc / alpha_bad come from the host
-// (fk_trip_consts: the values the ANN kernel's round trip uses too).
-struct FkTrip {
-  double jc[16];
-  int alpha_bad;
-};
-
-__global__ void robot_const_kernel(RobotDev r, FkTrip t, RobotConstDev *rc) {
-  if (threadIdx.x != 0) return;
-  int st = IK_OK;
-  for (int k = 1; k < 4; ++k)
-    if (!angle_ok(r.dh[k])) st = IK_E_ANGLE_RANGE;
-  for (int k = 0; k < 4; ++k)
-    if (!angle_ok(r.dh[12 + k])) st = IK_E_ANGLE_RANGE;
-  for (int k = 0; k < 6; ++k) rc->lim[k] = r.lim[k];
-  for (int k = 0; k < 16; ++k) rc->jc[k] = t.jc[k];
-  rc->alpha_bad = t.alpha_bad;
-  rc->st = st;
-  // seed_closed's P_k: the seed chain at theta_1 = 0 (Rz(0) = I exactly)
-  {
-    const double th[4] = {0.0, r.dh[1], r.dh[2], r.dh[3]};
-    d3 P[4];
-    (void)fk_chain(r.dh, th, P);
-    for (int j = 0; j < 4; ++j) {
-      rc->P[j][0] = P[j].x;
-      rc->P[j][1] = P[j].y;
-      rc->P[j][2] = P[j].z;
-    }
-  }
-}
-
-void launch_robot_const(const RobotDev &r, RobotConstDev *rc, hipStream_t stream) {
-  FkTrip t;
-  fk_trip_consts(r, t.jc, &t.alpha_bad);
-  IK_LAUNCH(robot_const_kernel, dim3(1), dim3(64), 0, stream, r, t, rc);
-}
 
 __device__ __forceinline__ void store_joints(double *dst, int64_t i, const d3 J[4]) {
   double *p = dst + 12 * i;
@@ -291,42 +43,6 @@ __device__ __forceinline__ void store_joints(double *dst, int64_t i, const d3 J[
     p[3 * k + 2] = J[k].z;
   }
 }
-
-__device__ __forceinline__ void load_joints(const double *src, int64_t i, d3 J[4]) {
-  const double2 *p = reinterpret_cast<const double2 *>(src + 12 * i);
-  double2 v0 = p[0], v1 = p[1], v2 = p[2], v3 = p[3], v4 = p[4], v5 = p[5];
-  J[0] = {v0.x, v0.y, v1.x};
-  J[1] = {v1.y, v2.x, v2.y};
-  J[2] = {v3.x, v3.y, v4.x};
-  J[3] = {v4.y, v5.x, v5.y};
-}
-
-
-struct FabArgs {
-  RobotDev r;
-  const RobotConstDev *rc;  // seed constants (robot_const_kernel)
-  const double *pts;
-  int64_t n;
-  double tol;      // fabrik.py:57 err_margin, as given
-  double tol2;     // tol_threshold(tol): the loop compares squared errors with it
-  ErrBand band;    // the lazy errors' band (fabrik_band) for lanes with |J0|_1 + |goal|_1 <= band_n1
-  double band_n1;
-  double qmax;     // the core-domain test on the quotients (fabrik_qmax)
-  int max_iter;
-  int check_limits;
-  double *ang;
-  int32_t *iters;   // nullable
-  double *joints;   // final joints n x 12 (nullable)
-  double *fk_err;   // |FK(theta) - p| per point (nullable; max/sum into S)
-  DevStats *S;
-  int chunk;        // work-queue grab size of the persistent iteration kernel (1..64)
-  // hard-first ordering (see "Work order" below); unused when perm is null
-  int32_t *perm;    // queue position -> point index
-  uint16_t *cell;   // per point: goal cell (bits 0-9) | cost class << 10
-  FabOrderDev *ord; // context-owned cost table
-  int prior_gate;   // the table is a built-in prior no call has taught yet (see scatter)
-  unsigned long long *dbg;  // diagnostic build only: iteration-kernel counters
-};
 
 // Diagnostic counters of the iteration kernel (-DIKHIP_DIAG, libikhip_diag.so,
 // tools/fabrik_diag.py): per wave, summed into dbg[0..7], and per wave w at
@@ -471,7 +187,7 @@ __global__ __launch_bounds__(256) void fabrik_simple_kernel(FabArgs a) {
       atomicMin(&a.S->first_oob, (unsigned long long)i);
     // Seed pose, inverse.py:123-130: FK of [atan2(y, x), thetas[1:]] (the
     // reference writes theta_1 into dh_matrix[0][0] and runs fkine on that row), in
-    // closed form from the per-robot constants (seed_closed, ik_common.h; r05 and
+    // closed form from the per-robot constants (seed_closed, ik_fk_chain.h; r05 and
     // before: seed_chain, the DH chain's own products).
     st = seed_closed(a.rc, g, J);
     double se = 1.0, ge = 1.0;
@@ -517,221 +233,8 @@ __device__ __forceinline__ void solve_general(const FabArgs &a, d3 g, d3 J[4], i
 // is kept for an in-loop redo).
 constexpr int kStRedo = 0x40;
 
-// ---------------------------------------------------------- Work order ----
-// The persistent iteration kernel hands points out in queue order.  In point
-// order a 100-iteration point can be picked up just before the queue runs dry
-// and set the launch length alone (≈ 1.4x the lane-iterations / lanes bound
-// at 1M random_dist points).  Handing out the expensive points first removes
-// most of that tail.  The cost of a point is predicted from its goal cell --
-// distance from the shoulder (the seed's first joint) in 64 bins up to the reach
-// of links 1..3, and the sine of the elevation in 16 bins -- by the LARGEST
-// iteration count the context recorded in that cell on earlier calls (1 point
-// in kOrdSample; the old key decays by 1/8 when new records arrive).  The
-// largest, not the mean: what sets the tail is a long point starting late, and
-// long points (9 % of random_dist points take >= 80 of 100 iterations) sit in
-// cells of every mean.  A list-scheduling simulation of 131k lanes on 1M
-// reference iteration counts (tol 1e-3 / 1e-5): point order 1.29x / 1.34x the
-// lane-iterations / lanes bound, cells by mean 1.15x / 1.23x, cells by sampled
-// max 1.04x / 1.03x, exact longest-first 1.01x.  Unseen cells count as hard.
-// Costs map to 16 classes; a counting sort (class-major, hardest first; order
-// inside a class is whatever the atomics give) yields the queue -> point
-// permutation.  Results do not depend on the order: every point is still
-// solved by the same arithmetic on its own.
-//
-// Launches: classify (cell + class per point from the goal alone, class totals)
-// -> scatter (class region starts from the totals, one cursor per class: the
-// queue -> point permutation) -> iterate (records 1 point in kOrdSample) -> fold
-// (one block: this call's records into the table for the next call).
-// 16 at 1M points: classify + scatter 28.8 us against 34.2 for 8 (table reads early)
-// and 49.0 for 4 (same box)
-#ifndef IKHIP_ORD_PPT
-#define IKHIP_ORD_PPT 16
-#endif
-constexpr int kOrdPPT = IKHIP_ORD_PPT;  // points per thread of the classify / scatter blocks
-// (r04: classify and scatter in one launch, the queue in per-class regions of n
-// entries: the launch takes 17.8 us against 13.5 + 9.8, but its queue order inside a
-// cost class makes the iteration kernel 4 % slower at tol 1e-3 with the same learned
-// table; dropped, profiles/r04/ab/fabrik_fused_scatter.txt)
-// (r04: spreading a block's class run over its slots -- slot r * 4099 mod run length --
-// so that a grab's points come from the whole block: iteration kernel +0.9 %, scatter
-// +3 us; profiles/r04/ab/fabrik_order_spread_dropped.txt)
-
-// The shoulder (the seed's first joint, the translation of A_1) is
-// (a1 cos t1, a1 sin t1, d1) with t1 the goal's own azimuth: its distance from the
-// goal needs no trigonometry.
-__device__ __forceinline__ int goal_cell(const RobotDev &r, d3 g) {
-  const double rxy = sqrt(g.x * g.x + g.y * g.y) - r.dh[8];
-  const double dz = g.z - r.dh[4];
-  const double dist = sqrt(rxy * rxy + dz * dz);
-  const double reach = r.links[1] + r.links[2] + r.links[3];
-  int rb = (int)(dist / reach * kOrdCellsR);
-  rb = rb < 0 ? 0 : (rb >= kOrdCellsR ? kOrdCellsR - 1 : rb);
-  int eb = dist > 0.0 ? (int)((dz / dist + 1.0) * (0.5 * kOrdCellsE)) : kOrdCellsE / 2;
-  eb = eb < 0 ? 0 : (eb >= kOrdCellsE ? kOrdCellsE - 1 : eb);
-  return rb * kOrdCellsE + eb;
-}
-
-__device__ __forceinline__ int key_class(unsigned int key, int max_iter) {
-  // key: 1 + largest recorded iterations, 0 = unseen
-  if (key == 0) return kOrdClasses - 1;
-  const int k = (int)((long long)(key - 1) * kOrdClasses / (max_iter + 1));
-  return k < 0 ? 0 : (k >= kOrdClasses ? kOrdClasses - 1 : k);
-}
-
-
-// Fold ns records into the table: per cell, the largest recorded iteration
-// count of the call, or the decayed old key if larger.  One block.
-__device__ void order_fold(FabOrderDev *T, unsigned int ns) {
-  __shared__ unsigned int lm[kOrdCells];
-  const int t = threadIdx.x;
-  for (int c = t; c < kOrdCells; c += blockDim.x) lm[c] = 0;
-  __syncthreads();
-  constexpr int kFoldBatch = 8;  // independent loads in flight
-  for (unsigned int k0 = t; k0 < ns; k0 += blockDim.x * kFoldBatch) {
-    unsigned int v[kFoldBatch];
-#pragma unroll
-    for (int j = 0; j < kFoldBatch; ++j) {
-      const unsigned int k = k0 + blockDim.x * j;
-      v[j] = k < ns ? T->sample[k] : 0xffffffffu;
-    }
-#pragma unroll
-    for (int j = 0; j < kFoldBatch; ++j)
-      if (v[j] != 0xffffffffu) atomicMax(&lm[v[j] >> 16], (v[j] & 0xffffu) + 1u);
-  }
-  __syncthreads();
-  for (int c = t; c < kOrdCells; c += blockDim.x) {
-    if (lm[c]) {
-      const unsigned int old = T->key[c];
-      const unsigned int dec = old - (old >> 3);
-      T->key[c] = lm[c] > dec ? lm[c] : dec;
-    }
-  }
-}
-
-// 1. classify: the goal's cell and cost class per point (2 bytes), and the
-// class totals (one atomic per class and block, into the block's shard: one
-// address per class took ~1k same-address atomics per launch at 1M points).
-// The cell -> class map of this call is built in LDS first.
-__global__ __launch_bounds__(256) void fabrik_classify_kernel(FabArgs a) {
-  __shared__ unsigned int cnt[kOrdClasses], unseen;
-  __shared__ uint8_t cls[kOrdCells];  // the cell's class, 0xff: unseen (the hardest class)
-  const int t = threadIdx.x;
-  const int64_t b0 = (int64_t)blockIdx.x * (256 * kOrdPPT);
-  d3 g[kOrdPPT];
-#pragma unroll
-  for (int j = 0; j < kOrdPPT; ++j) {  // all loads in flight before the first use
-    const int64_t i = b0 + j * 256 + t;
-    if (i < a.n) g[j] = {a.pts[3 * i], a.pts[3 * i + 1], a.pts[3 * i + 2]};
-  }
-  if (t < kOrdClasses) cnt[t] = 0;
-  if (t == 0) unseen = 0;
-  // the cell -> class map's table reads, in flight with the goals'
-  static_assert(kOrdCells % 256 == 0, "whole table rows per thread");
-  unsigned int key[kOrdCells / 256];
-#pragma unroll
-  for (int q = 0; q < kOrdCells / 256; ++q) key[q] = a.ord->key[t + 256 * q];
-#pragma unroll
-  for (int q = 0; q < kOrdCells / 256; ++q)
-    cls[t + 256 * q] = key[q] ? (uint8_t)key_class(key[q], a.max_iter) : (uint8_t)0xff;
-  __syncthreads();
-  unsigned int nu = 0;
-#pragma unroll
-  for (int j = 0; j < kOrdPPT; ++j) {
-    const int64_t i = b0 + j * 256 + t;
-    if (i < a.n) {
-      const int cell = goal_cell(a.r, g[j]);
-      int k = cls[cell];
-      nu += k == 0xff ? 1u : 0u;
-      k = k == 0xff ? kOrdClasses - 1 : k;
-      a.cell[i] = (uint16_t)(cell | (k << 10));
-      atomicAdd(&cnt[k], 1u);
-    }
-  }
-  // (only the prior's gate reads the count: the first call of a context; a
-  // wave sum, then one LDS atomic per wave -- one per thread cost 2 us a launch)
-  if (a.prior_gate) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nu += __shfl_xor(nu, off, 64);
-    if ((t & 63) == 0 && nu) atomicAdd(&unseen, nu);
-  }
-  __syncthreads();
-  if (t < kOrdClasses && cnt[t]) atomicAdd(&a.S->cls_tot[t][blockIdx.x % kOrdShards], cnt[t]);
-  if (t == 0 && unseen) atomicAdd(&a.S->unseen, (unsigned long long)unseen);
-}
-
-// The built-in prior's gate: a table no call has taught yet is
-// the prior learned on random_dist batches (ik_fabrik_prior.h).  On a batch of
-// another distribution many goals fall in cells it has never seen (uniform box:
-// the unreachable far cells; a spring trajectory: the far end of its curve), and
-// ordering by it measured slower than point order (r06 lease: uniform box +1.5 %,
-// spring +2.3 %).  When more than 1 / kPriorUnseenDiv of the batch lands in unseen
-// cells, the first call keeps point order; the call's records then teach the
-// table as usual.
-constexpr unsigned kPriorUnseenDiv = 50;
-
-// 2. scatter: perm[queue position] = point.  The queue is class-major (hardest
-// first), then shard: region (c, s) starts after every harder class and every
-// lower shard of class c.  Block b covers the points classify's block b counted
-// into shard b % kOrdShards, claims its run inside its region with one atomic
-// per class and hands the slots out through LDS atomics.
-__global__ __launch_bounds__(256) void fabrik_scatter_kernel(FabArgs a) {
-  static_assert(kOrdClasses * kOrdShards == 256, "one total per thread");
-  // the prior does not describe this batch (see above): every point in the last
-  // class, i.e. the order an empty table gives (block shards, point order inside)
-  const bool gated = a.prior_gate && a.S->unseen * kPriorUnseenDiv > (unsigned long long)a.n;
-  __shared__ unsigned int cnt[kOrdClasses], base[kOrdClasses];
-  __shared__ unsigned int tot[kOrdClasses][kOrdShards], ctot[kOrdClasses];
-  const int t = threadIdx.x;
-  const int sh = blockIdx.x % kOrdShards;
-  if (t < kOrdClasses) cnt[t] = 0;
-  // the 256 (class, shard) totals, one load per thread, in flight with the cells
-  tot[t / kOrdShards][t % kOrdShards] = (&a.S->cls_tot[0][0])[t];
-  const int64_t b0 = (int64_t)blockIdx.x * (256 * kOrdPPT);
-  uint16_t cl[kOrdPPT];
-#pragma unroll
-  for (int j = 0; j < kOrdPPT; ++j) {
-    const int64_t i = b0 + j * 256 + t;
-    cl[j] = i < a.n ? a.cell[i] : (uint16_t)0xffff;
-    if (gated && cl[j] != 0xffff) cl[j] |= (uint16_t)((kOrdClasses - 1) << 10);
-  }
-  __syncthreads();
-  if (gated) {  // (uniform) the shards' totals all in the last class
-    unsigned int col = 0;
-    if (t < kOrdShards)
-      for (int c = 0; c < kOrdClasses; ++c) col += tot[c][t];
-    __syncthreads();
-    if (t < kOrdShards)
-      for (int c = 0; c < kOrdClasses; ++c) tot[c][t] = c == kOrdClasses - 1 ? col : 0u;
-    __syncthreads();
-  }
-#pragma unroll
-  for (int j = 0; j < kOrdPPT; ++j)
-    if (cl[j] != 0xffff) atomicAdd(&cnt[cl[j] >> 10], 1u);
-  if (t < kOrdClasses) {
-    unsigned int c = 0;
-#pragma unroll
-    for (int q = 0; q < kOrdShards; ++q) c += tot[t][q];
-    ctot[t] = c;
-  }
-  __syncthreads();
-  if (t < kOrdClasses) {
-    // region (t, sh) starts after every harder class and the lower shards of t
-    unsigned int start = 0;
-    for (int c = kOrdClasses - 1; c > t; --c) start += ctot[c];
-    for (int q = 0; q < sh; ++q) start += tot[t][q];
-    base[t] = start + (cnt[t] ? atomicAdd(&a.S->cls_cur[t][sh], cnt[t]) : 0u);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kOrdPPT; ++j) {
-    if (cl[j] != 0xffff) {
-      const unsigned int pos = atomicAdd(&base[cl[j] >> 10], 1u);
-      a.perm[pos] = (int32_t)(b0 + j * 256 + t);
-    }
-  }
-}
-
-// 3. persistent iteration with per-lane refill, seed and angles in batches.
+// Persistent iteration with per-lane refill, seed and angles in batches (the work
+// order's launch 3, between scatter and fold: ik_fabrik_order.hip).
 //
 // A lane whose point converged is refilled from the wave's batch of prepared
 // points: a wave grabs a.chunk queue positions at once and each lane prepares one
@@ -847,7 +350,7 @@ __device__ __forceinline__ void ring_flush(const FabArgs &a, RetireRing &R, int 
 }
 
 
-// ORD: the queue is a.perm (work order above), else point order.  CORE: 0
+// ORD: the queue is a.perm (ik_fabrik_order.hip), else point order.  CORE: 0
 // general sqrt / division, 1 sqrt_core / div_core, 2 the same with the repeated
 // distances taken once and the loop condition from the band (fabrik_step4_lazy;
 // needs L0 == L1 and L2 == L3).
@@ -1291,14 +794,6 @@ fabrik_iter_kernel(FabArgs a) {
   // XCD's L2 back while the last waves were still draining, r03)
 }
 
-// The cost-table fold after an ordered solve (one block): this call's samples
-// (the retire steps' stores, published by the kernel boundary) into the table
-// the next call's classify reads.
-__global__ __launch_bounds__(256) void fabrik_fold_kernel(FabArgs a) {
-  const int64_t ns = (a.n + kOrdSample - 1) / kOrdSample;
-  order_fold(a.ord, (unsigned int)(ns < kOrdMaxSample ? ns : kOrdMaxSample));
-}
-
 static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 size_t fabrik_scratch_bytes(int64_t n) {
@@ -1379,12 +874,7 @@ void launch_fabrik_ikine(const RobotDev &r, const double *pts, int64_t n, double
     a.perm = reinterpret_cast<int32_t *>(sp);
     sp += up256((size_t)n * 4);
     a.cell = reinterpret_cast<uint16_t *>(sp);
-    kt_begin("fabrik_classify_kernel", stream);
-    IK_LAUNCH(fabrik_classify_kernel, dim3(p.ogrid), dim3(256), 0, stream, a);
-    kt_end(stream);
-    kt_begin("fabrik_scatter_kernel", stream);
-    IK_LAUNCH(fabrik_scatter_kernel, dim3(p.ogrid), dim3(256), 0, stream, a);
-    kt_end(stream);
+    launch_fabrik_order(a, p.ogrid, stream);
   }
 #ifdef IKHIP_DIAG
   if (a.dbg) (void)hipMemsetAsync(a.dbg, 0, kFabrikDebugWords * 8, stream);
@@ -1398,142 +888,7 @@ void launch_fabrik_ikine(const RobotDev &r, const double *pts, int64_t n, double
     else launch_iter<IKHIP_FAB_REFILL, false>(p.core, p.pgrid, stream, a);
   }
   kt_end(stream);
-  if (p.ordered) {
-    kt_begin("fabrik_fold_kernel", stream);
-    IK_LAUNCH(fabrik_fold_kernel, dim3(1), dim3(256), 0, stream, a);
-    kt_end(stream);
-  }
-}
-
-// ------------------------------------------------------ Fabrik.calculate ----
-template <int NJ>
-__global__ __launch_bounds__(256) void fabrik_calc_kernel(const double *dists_in,
-                                                          const double *init, int shared,
-                                                          const double *goals, int64_t n,
-                                                          double tol2, int max_iter,
-                                                          double *joints, int32_t *iters,
-                                                          DevStats *S) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool valid = i < n;
-  int it = 0;
-  if (valid) {
-    double L[NJ];
-#pragma unroll
-    for (int k = 0; k < NJ; ++k) L[k] = dists_in[k];
-    const double *ip = shared ? init : init + (size_t)i * NJ * 3;
-    d3 cur[NJ], B[NJ];
-#pragma unroll
-    for (int k = 0; k < NJ; ++k) cur[k] = {ip[3 * k], ip[3 * k + 1], ip[3 * k + 2]};
-    d3 g = {goals[3 * i], goals[3 * i + 1], goals[3 * i + 2]};
-    const d3 start = cur[0];
-    double se = 1.0, ge = 1.0;
-    int st = IK_OK;
-    while (((se > tol2) || (ge > tol2)) && (max_iter > it)) {  // squared errors
-      B[NJ - 1] = g;
-#pragma unroll
-      for (int k = NJ - 2; k >= 0; --k) B[k] = point_between(B[k + 1], cur[k], L[k], st);
-      se = dist3_sq(B[0], start);
-      cur[0] = start;
-#pragma unroll
-      for (int k = 1; k < NJ; ++k) cur[k] = point_between(cur[k - 1], B[k], L[k], st);
-      ge = dist3_sq(cur[NJ - 1], g);
-      ++it;
-      if (st != IK_OK) break;
-    }
-    if (st != IK_OK) record_error(S, i, st);
-    double *o = joints + (size_t)i * NJ * 3;
-#pragma unroll
-    for (int k = 0; k < NJ; ++k) {
-      o[3 * k] = cur[k].x;
-      o[3 * k + 1] = cur[k].y;
-      o[3 * k + 2] = cur[k].z;
-    }
-    if (iters) iters[i] = it;
-  }
-  block_iter_stats(S, valid, it, max_iter);
-}
-
-// Any chain length (1 joint up, fabrik.py:44-67 takes any len(init) ==
-// len(dists)): the chain lives in the lane's output row instead of registers.
-// The backward pass writes B[k] over cur[k] (cur[k] is read only to form B[k]),
-// and the forward pass writes the new cur[k] over B[k] (read only to form it),
-// so one nj x 3 row per point holds both passes.  Same point_between calls in the
-// same order as the unrolled kernel: the same bits.
-__global__ __launch_bounds__(256) void fabrik_calc_any_kernel(int nj, const double *dists,
-                                                              const double *init, int shared,
-                                                              const double *goals, int64_t n,
-                                                              double tol2, int max_iter,
-                                                              double *joints, int32_t *iters,
-                                                              DevStats *S) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool valid = i < n;
-  int it = 0;
-  if (valid) {
-    const double *ip = shared ? init : init + (size_t)i * nj * 3;
-    double *row = joints + (size_t)i * nj * 3;
-    auto ld = [&](const double *p, int k) -> d3 { return {p[3 * k], p[3 * k + 1], p[3 * k + 2]}; };
-    auto stj = [&](int k, d3 v) {
-      row[3 * k] = v.x;
-      row[3 * k + 1] = v.y;
-      row[3 * k + 2] = v.z;
-    };
-    for (int k = 0; k < nj; ++k) stj(k, ld(ip, k));
-    const d3 g = {goals[3 * i], goals[3 * i + 1], goals[3 * i + 2]};
-    const d3 start = ld(ip, 0);
-    double se = 1.0, ge = 1.0;
-    int st = IK_OK;
-    while (((se > tol2) || (ge > tol2)) && (max_iter > it)) {  // squared errors
-      d3 b = g;  // B[nj - 1]
-      stj(nj - 1, b);
-      for (int k = nj - 2; k >= 0; --k) {
-        b = point_between(b, ld(row, k), dists[k], st);
-        stj(k, b);
-      }
-      se = dist3_sq(b, start);  // B[0]
-      d3 f = start;
-      stj(0, f);
-      for (int k = 1; k < nj; ++k) {
-        f = point_between(f, ld(row, k), dists[k], st);
-        stj(k, f);
-      }
-      ge = dist3_sq(f, g);
-      ++it;
-      if (st != IK_OK) break;
-    }
-    if (st != IK_OK) record_error(S, i, st);
-    if (iters) iters[i] = it;
-  }
-  block_iter_stats(S, valid, it, max_iter);
-}
-
-void launch_fabrik_calc(int nj, const double *dists, const double *init, bool init_shared,
-                        const double *goals, int64_t n, double tol, int max_iter,
-                        double *joints, int32_t *iters, DevStats *S, hipStream_t st) {
-  if (n <= 0) return;
-  unsigned grid = (unsigned)((n + 255) / 256);
-  int sh = init_shared ? 1 : 0;
-  const double tol2 = tol_threshold(tol);
-#define IK_CALC_CASE(K)                                                                      \
-  case K:                                                                                    \
-    IK_LAUNCH(fabrik_calc_kernel<K>, dim3(grid), dim3(256), 0, st, dists, init, sh, \
-                       goals, n, tol2, max_iter, joints, iters, S);                          \
-    break;
-  kt_begin("fabrik_calc_kernel", st);
-  switch (nj) {
-    IK_CALC_CASE(2)
-    IK_CALC_CASE(3)
-    IK_CALC_CASE(4)
-    IK_CALC_CASE(5)
-    IK_CALC_CASE(6)
-    IK_CALC_CASE(7)
-    IK_CALC_CASE(8)
-    default:
-      IK_LAUNCH(fabrik_calc_any_kernel, dim3(grid), dim3(256), 0, st, nj, dists, init,
-                         sh, goals, n, tol2, max_iter, joints, iters, S);
-      break;
-  }
-  kt_end(st);
-#undef IK_CALC_CASE
+  if (p.ordered) launch_fabrik_fold(a, stream);
 }
 
 }  // namespace ikhip

@@ -56,7 +56,7 @@ double fabrik_qmax(const double *L) {
 }
 
 FabPlan fabrik_plan(const FabPlanIn &in) {
-  constexpr double kPi = 3.141592653589793;  // math.pi (ik_common.h)
+  constexpr double kPi = 3.141592653589793;  // math.pi (ik_types.h)
   const int64_t n = in.n;
   FabPlan p;
   p.tol2 = tol_threshold(in.tol);

@@ -4,8 +4,12 @@
 // (tools/ubench.hip).  Bit-exactness notes: DESIGN.md "FABRIK".
 #pragma once
 
-#include "ik_common.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ik_arith.h"
 #include "ik_fabrik_plan.h"
+#include "ik_types.h"
 
 namespace ikhip {
 

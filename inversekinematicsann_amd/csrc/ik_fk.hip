@@ -1,11 +1,16 @@
 // ik_fk.hip -- batched forward kinematics and workspace check.
 //
 // fk_kernel restates ForwardKinematics.fkine (kinematics/forward.py:73-94)
-// for a batch: one point per lane, the DH chain in float64 (ik_common.h).
+// for a batch: one point per lane, the DH chain in float64 (ik_fk_chain.h).
 // HBM traffic per point: 32 B angles in + 24 B xyz out (+96 B joints if asked).
+// The per-context kernels live here too: the stats reset, the workspace check and
+// the robot's constants.
 #include <cmath>
 
-#include "ik_common.h"
+#include "ik_fk.h"
+#include "ik_fk_chain.h"
+#include "ik_launch.h"
+#include "ik_stats.h"
 
 namespace ikhip {
 
@@ -50,6 +55,43 @@ void launch_check_limits(const RobotDev &r, const double *pts, int64_t n, DevSta
   kt_begin("check_limits_kernel", st);
   IK_LAUNCH(check_limits_kernel, dim3(grid), dim3(256), 0, st, r, pts, n, S);
   kt_end(st);
+}
+
+// The per-robot constants (RobotConstDev).  jc / alpha_bad come from the host
+// (fk_trip_consts: the values the ANN kernel's round trip uses too).
+struct FkTrip {
+  double jc[16];
+  int alpha_bad;
+};
+
+__global__ void robot_const_kernel(RobotDev r, FkTrip t, RobotConstDev *rc) {
+  if (threadIdx.x != 0) return;
+  int st = IK_OK;
+  for (int k = 1; k < 4; ++k)
+    if (!angle_ok(r.dh[k])) st = IK_E_ANGLE_RANGE;
+  for (int k = 0; k < 4; ++k)
+    if (!angle_ok(r.dh[12 + k])) st = IK_E_ANGLE_RANGE;
+  for (int k = 0; k < 6; ++k) rc->lim[k] = r.lim[k];
+  for (int k = 0; k < 16; ++k) rc->jc[k] = t.jc[k];
+  rc->alpha_bad = t.alpha_bad;
+  rc->st = st;
+  // seed_closed's P_k: the seed chain at theta_1 = 0 (Rz(0) = I exactly)
+  {
+    const double th[4] = {0.0, r.dh[1], r.dh[2], r.dh[3]};
+    d3 P[4];
+    (void)fk_chain(r.dh, th, P);
+    for (int j = 0; j < 4; ++j) {
+      rc->P[j][0] = P[j].x;
+      rc->P[j][1] = P[j].y;
+      rc->P[j][2] = P[j].z;
+    }
+  }
+}
+
+void launch_robot_const(const RobotDev &r, RobotConstDev *rc, hipStream_t stream) {
+  FkTrip t;
+  fk_trip_consts(r, t.jc, &t.alpha_bad);
+  IK_LAUNCH(robot_const_kernel, dim3(1), dim3(64), 0, stream, r, t, rc);
 }
 
 // The effector from the closed form of each DH matrix,

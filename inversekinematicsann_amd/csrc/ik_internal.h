@@ -9,11 +9,19 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <initializer_list>
 #include <string>
 
-#include "ik_common.h"
+#include "../../include/ikhip.h"
+#include "ik_ann.h"
+#include "ik_ann_pack.h"
+#include "ik_fabrik.h"
+#include "ik_launch.h"
+#include "ik_refine_step.h"
+#include "ik_train.h"
+#include "ik_types.h"
 
 namespace ikhip {
 constexpr int kMaxTimed = 64;  // kernels timed per call (the layered ANN path launches one per layer)

@@ -17,7 +17,9 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "ik_fabrik.h"
 #include "ik_internal.h"
+#include "ik_types.h"
 
 using namespace ikhip;
 

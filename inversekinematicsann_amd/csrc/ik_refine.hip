@@ -17,8 +17,11 @@
 // The wave iterates until no lane is active; a finished lane keeps its angles (the
 // update is a select) and recomputes the same error.  HBM per row: 24 B goal +
 // 32 / 16 B seed in, 32 B angles (+ 4 B count + 8 B error) out.
-#include "ik_common.h"
+#include "ik_fk_chain.h"
+#include "ik_launch.h"
+#include "ik_refine.h"
 #include "ik_refine_step.h"
+#include "ik_stats.h"
 
 namespace ikhip {
 

@@ -39,8 +39,12 @@
 #include <string>
 #include <thread>
 
+#include "ik_fabrik.h"
+#include "ik_fk.h"
 #include "ik_internal.h"
+#include "ik_launch.h"
 #include "ik_shard_plan.h"
+#include "ik_types.h"
 
 using namespace ikhip;
 using namespace ikapi;

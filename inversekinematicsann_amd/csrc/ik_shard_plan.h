@@ -17,7 +17,7 @@ void part_of(const ik_shard_plan &p, int r, int c, int64_t *b, int64_t *e);
 // Rank order, as one process would meet the points: the lowest global failing
 // index wins, sums add up, FK-error max over ranks.
 void tail_reduce(const ik_shard_tail *t, int nranks, ik_stats *s);
-// The upper edge of a histogram bin (fkhist_bin, ik_common.h): 0 below the
+// The upper edge of a histogram bin (fkhist_bin, ik_types.h): 0 below the
 // first, HUGE_VAL from the last.
 double fkhist_upper(int bin);
 // The upper edge of the bin holding the ceil(q m)-th smallest of the m errors

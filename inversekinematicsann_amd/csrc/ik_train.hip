@@ -31,7 +31,9 @@
 #include <cstdint>
 
 #include "ik_act.h"
-#include "ik_common.h"
+#include "ik_fk_chain.h"
+#include "ik_launch.h"
+#include "ik_train.h"
 #include "ik_train_fk_row.h"
 
 namespace ikhip {

@@ -11,6 +11,8 @@
 #include <vector>
 
 #include "ik_internal.h"
+#include "ik_train.h"
+#include "ik_train_plan.h"
 
 using namespace ikhip;
 using namespace ikapi;

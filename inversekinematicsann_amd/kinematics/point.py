@@ -2,7 +2,7 @@
 
 These are host-side VALUE helpers kept for API compatibility (the reference's
 tests/point_unit.py exercises them); no batched solve goes through them -- on
-the GPU the same arithmetic runs inside the FABRIK kernel (csrc/ik_common.h
+the GPU the same arithmetic runs inside the FABRIK kernel (csrc/ik_arith.h
 dist3 / point_between).
 """
 from __future__ import annotations

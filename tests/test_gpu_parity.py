@@ -647,7 +647,7 @@ def test_ann_dropin_api():
 
 
 def test_fabrik_work_order_is_invisible():
-    """The hard-first work order (ik_fabrik.hip "Work order") only changes which
+    """The hard-first work order (ik_fabrik_order.hip "Work order") only changes which
     point a lane takes when: results are bit-identical from call to call while
     the cost table learns, across batch sizes with different histogram segment
     counts, and iteration counts stay equal to the oracle's."""
@@ -684,7 +684,7 @@ def test_fabrik_prior_gate_first_call_other_distributions():
     """a fresh context's first call on a batch the built-in table
     was not learned on (uniform workspace box, a spring trajectory; most goals in
     cells the prior has never seen) keeps the empty table's order (the scatter's
-    gate, ik_fabrik.hip) -- and, gated or not, the results are the oracle's bit for
+    gate, ik_fabrik_order.hip) -- and, gated or not, the results are the oracle's bit for
     bit in the counts, identical to an empty-table solve, and the call teaches
     the table as usual."""
     from inversekinematicsann_amd import _native
@@ -764,7 +764,7 @@ def test_device_pointer_path(ctx1):
 
 
 def test_fabrik_core_sequences_bit_identical():
-    """The iteration kernel's sqrt_core / div_core path (ik_common.h), alone (1) and
+    """The iteration kernel's sqrt_core / div_core path (ik_arith.h), alone (1) and
     with the repeated distances taken once (2, fabrik_step4_reuse), claims the
     same bits as the general sqrt / division wherever its domain check passes,
     and falls back per wave elsewhere: final joints and iteration counts of the

@@ -15,7 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "../inversekinematicsann_amd/csrc/ik_common.h"
+#include "../inversekinematicsann_amd/csrc/ik_arith.h"
 
 using namespace ikhip;
 

@@ -17,7 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "../inversekinematicsann_amd/csrc/ik_common.h"
+#include "../inversekinematicsann_amd/csrc/ik_arith.h"
 #include "quot_fused.h"
 
 using namespace ikhip;

@@ -10,7 +10,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "../inversekinematicsann_amd/csrc/ik_common.h"
+#include "../inversekinematicsann_amd/csrc/ik_arith.h"
 #include "quot_fused.h"
 
 using namespace ikhip;

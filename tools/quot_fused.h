@@ -6,12 +6,12 @@
 // that the record can be reproduced; the product never used it.
 #pragma once
 
-#include "../inversekinematicsann_amd/csrc/ik_common.h"
+#include "../inversekinematicsann_amd/csrc/ik_arith.h"
 
 namespace ikhip {
 
 __device__ __forceinline__ double quot_sqrt_core(double a, double x) {
-  // sqrt_core's sequence (ik_common.h), keeping h
+  // sqrt_core's sequence (ik_arith.h), keeping h
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y;
   double h = y * 0.5;

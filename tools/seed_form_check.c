@@ -1,5 +1,5 @@
 /* seed_form_check.c -- evidence for the closed-form FABRIK seed (seed_closed,
- * csrc/ik_common.h): FABRIK iteration counts with the seed pose computed as
+ * csrc/ik_fk_chain.h): FABRIK iteration counts with the seed pose computed as
  * J_k = Rz(theta_1) P_k, cos / sin(theta_1) = (x, y) / |(x, y)|, against the
  * oracle's restatement of the reference chain (inverse.py:123-130 -> fk_chain),
  * point by point, in float64 on the CPU.  Test infrastructure (includes the

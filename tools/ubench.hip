@@ -447,7 +447,7 @@ static void timed(const char *name, F launch, unsigned long long *dclk, double w
 }
 
 int main(int argc, char **argv) {
-  const int cus = ::num_cus();  // (ik_common.h has one of its own in ikhip::)
+  const int cus = ::num_cus();  // (ik_launch.h has one of its own in ikhip::)
   double *dout = nullptr, *dgoals = nullptr;
   unsigned long long *dclk = nullptr;
   CK(hipMalloc(&dout, (size_t)cus * 8 * 256 * 8));
