@@ -252,6 +252,71 @@ int ik_get_joint_limits(ik_ctx *ctx, double *lo /*4*/, double *hi /*4*/);
 int ik_check_joint_limits(ik_ctx *ctx, const double *ang /*n x 4*/, int64_t n, int flags,
                           ik_stats *stats);
 
+/* ---- Chain solve ---------------------------------------------------------------
+ * Inverse kinematics of any DH table of NJ = nj (2..8) revolute joints, float64: the
+ * refine above with NJ where it says 4, joint limits per joint, and restarts from
+ * random points, since a general chain has no trained network to seed it.  dh (4 x nj
+ * row-major: theta, d, a, alpha), lo and hi (nj each, both NULL: every joint free) are
+ * always HOST pointers and are handed to the kernel by value, so an IK_F_ASYNC call
+ * uploads nothing and adds no sync.  The context's robot, its workspace limits and its
+ * stored joint limits are neither read nor changed: first_oob is always -1 and
+ * IK_F_NO_LIMITS has no effect.  pts n x 3, seed (nullable) n x nj, ang n x nj, iters /
+ * tries (nullable) n int32, fk_err (nullable) n float64 follow the usual host /
+ * IK_F_DEVICE / IK_F_ASYNC convention.  Rows of ang are nj doubles; for odd nj they
+ * are not 16-byte aligned, the kernel uses 8-byte accesses and this call does NOT
+ * demand an aligned ang.  Per row:
+ *   constants: per joint {a, d, cos alpha, sin alpha}, std::cos / std::sin on the host
+ *     in float64.  Some |alpha_i| > 2 pi: every error is NaN and no row takes a step,
+ *     as in ik_refine.
+ *   chain: the effector Rz(t_1) B_1 .. Rz(t_NJ) B_NJ e4, B_i = Tz(d_i) Tx(a_i)
+ *     Rx(alpha_i), applied right to left to a vector as a loop over the joints, the
+ *     open Jacobian columns riding along: column i is (-y', x', 0) of the vector just
+ *     rotated by Rz(t_i), then takes only the rotations to its left.  Column 1's z
+ *     entry is identically zero and is left out of every sum.
+ *   matrix: A = J' J'^T + damping^2 I, J' = J with the locked columns replaced by
+ *     +0.0; each of its six entries is a sum over the joints in joint order from joint
+ *     1's term (A20, A21 and A22 from joint 2's), damping^2 added last.
+ *   solve: LDL^T without pivoting; delta_i = jx q0 + jy q1 + jz q2 (joint 1:
+ *     jx q0 + jy q1).
+ *   update: m = fmax over all |delta_i|; m > 0.5: delta = delta (0.5 / m); a free
+ *     joint theta_i = wrap(theta_i + delta_i), a limited one clip(theta_i + delta_i).
+ *   limits: ik_set_joint_limits' rule per joint over nj joints; the seed is projected;
+ *     the active-set loop of "Joint limits" re-solves at most NJ times (on the device
+ *     it is wave-uniform).
+ *   seed: seed == NULL gives every row the table's theta row dh[0 .. nj-1], the home
+ *     pose.
+ *   restarts (0..255): attempt 0 starts from the seed.  An attempt ends like an
+ *     ik_refine row: !(err > tol), or max_iter steps of this attempt.  If it ends with
+ *     err > tol and attempts remain, attempt a >= 1 starts from
+ *       theta_j = lo'_j + u(row, a, j) (hi'_j - lo'_j),
+ *     [lo', hi'] the joint's limits or [-pi, pi] for a free joint, which then gets the
+ *     seed's treatment (wrap, and clip where limited), with
+ *       z = row * 0x9E3779B97F4A7C15 + ((a << 8) | j)      (uint64, wrapping; j = 0 .. nj-1)
+ *       z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *       z ^= z >> 31;  u = (double)(z >> 11) * 0x1p-53.
+ *     A NaN error ends the row at once with no restart.  The row returns the attempt
+ *     with the smallest final error, the earliest on a tie: its angles go to ang, its
+ *     error to fk_err, its index to tries; iters holds the steps of all attempts
+ *     together.
+ * At nj = 4, restarts = 0, the result is ik_refine's for the same table and limits, bit
+ * for bit.  stats: max_iters / sum_iters over iters, n_capped = rows with
+ * !(fk_err <= tol), first_err the lowest such row that has a finite error with
+ * first_err_code = IK_E_OUT_OF_REACH (-1: none), max_fk_err / sum_fk_err over the finite
+ * errors.  Converged lanes idle until their wave's slowest row ends: restarts multiply
+ * the worst row's steps, not the average's.
+ * IK_E_BADARG, the context left usable: nj outside 2..8 (longer chains are not built),
+ * a NULL dh, a non-finite entry in the d, a or alpha rows, the limit errors of
+ * ik_set_joint_limits naming the joint, exactly one of lo / hi NULL, restarts outside
+ * 0..255, max_iter (restarts + 1) above 2^31 - 1 (iters is an int32), and what ik_refine refuses (n < 0, a NULL pts / ang with n > 0, max_iter < 0,
+ * tol NaN, damping not finite or <= 0, IK_F_ASYNC without IK_F_DEVICE).  n == 0 is IK_OK
+ * with empty stats. */
+int ik_chain_solve(ik_ctx *ctx, int nj, const double *dh /*host, 4 x nj: theta, d, a, alpha*/,
+                   const double *lo /*host nj, nullable*/, const double *hi /*host nj, nullable*/,
+                   const double *pts /*n x 3*/, const double *seed /*n x nj, nullable*/, int64_t n,
+                   double tol, int32_t max_iter, double damping, int32_t restarts,
+                   double *ang /*n x nj*/, int32_t *iters /*nullable*/, int32_t *tries /*nullable*/,
+                   double *fk_err /*nullable*/, int flags, ik_stats *stats);
+
 /* ---- Analytic ----------------------------------------------------------------
  * Closed-form inverse kinematics with a chosen tool pitch and elbow branch, float64,
  * no iteration, for a context's robot that is a yaw joint followed by a planar

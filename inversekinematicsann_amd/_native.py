@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = ("ik_ctx_create", "ik_ctx_destroy", "ik_ctx_set_stream", "ik_
                     "ik_last_error", "ik_version", "ik_set_robot", "ik_check_limits", "ik_fk", "ik_fk_chain",
                     "ik_set_joint_limits", "ik_get_joint_limits", "ik_check_joint_limits",
                     "ik_fabrik_solve", "ik_fabrik_solve_fk", "ik_fabrik_calc", "ik_fabrik_reset_order", "ik_ann_load", "ik_ann_solve",
-                    "ik_refine", "ik_ann_solve_refined", "ik_analytic_solve",
+                    "ik_refine", "ik_ann_solve_refined", "ik_analytic_solve", "ik_chain_solve",
                     "ik_stats_fetch", "ik_ctx_set_timing", "ik_kernel_times",
                     "ik_ctx_set_debug", "ik_debug_read", "ik_ann_set_mode", "ik_ann_get_mode",
                     "ik_ann_effective_mode",
@@ -144,6 +144,8 @@ def load_library(path: str = LIB_PATH):
                                            ip, dp, dp, ctypes.c_int, st]
         L.ik_analytic_solve.argtypes = [vp, dp, dp, i64, ctypes.c_int, dp, dp, dp, ctypes.c_int,
                                         st]
+        L.ik_chain_solve.argtypes = [vp, ctypes.c_int, dp, dp, dp, dp, dp, i64, ctypes.c_double,
+                                     i32, ctypes.c_double, i32, dp, ip, ip, dp, ctypes.c_int, st]
         L.ik_stats_fetch.argtypes = [vp, st]
         L.ik_ctx_sync.argtypes = [vp]
         L.ik_comm_set_timeout.argtypes = [vp, ctypes.c_double]
@@ -622,6 +624,67 @@ class Context:
         self._on_torch_stream(lambda: self._check(self.lib.ik_ann_solve_refined(
             self.handle, args[0], n, float(tol), int(max_iter), float(damping), args[1], args[2],
             args[3], args[4], flags, ctypes.byref(s))))
+        return s
+
+    # -- chain solve (include/ikhip.h "Chain solve") ------------------------------
+    @staticmethod
+    def _chain_args(dh, joint_limits, max_iter, restarts):
+        """The host arguments of ik_chain_solve, checked before the library sees them
+        (kinematics/chain.py: the library's own refusals as ValueError): (dh 4 x nj,
+        lo or None, hi or None)."""
+        from .kinematics.chain import chain_dh, chain_limit_arrays, check_steps
+        d = np.ascontiguousarray(chain_dh(dh))
+        check_steps(max_iter, restarts)
+        if joint_limits is None:
+            return d, None, None
+        lo, hi = chain_limit_arrays(joint_limits, d.shape[1])
+        return d, np.ascontiguousarray(lo), np.ascontiguousarray(hi)
+
+    def chain_solve(self, dh, pts, seed=None, joint_limits=None, tol=1e-6, max_iter=60,
+                    damping=1e-3, restarts=0, want_iters=True, want_tries=True,
+                    want_fk_err=True):
+        """ik_chain_solve on host arrays: dh 4 x nj (2..8 joints), pts n x 3, seed n x nj
+        or None (the table's theta row), joint_limits None, a pair of numpy arrays
+        (lo[nj], hi[nj]) or nj entries, each a tuple / list (lo, hi) or None (told apart by
+        type, kinematics.chain.chain_limit_arrays: two numpy arrays are the pair, also
+        at nj == 2).  Returns (angles n x nj f64, iters, tries, fk_err,
+        stats); the context's robot and joint limits are not touched."""
+        d, lo, hi = self._chain_args(dh, joint_limits, max_iter, restarts)
+        nj = d.shape[1]
+        s = IkStats()
+        p = _host(pts, np.float64, 3)
+        n = p.shape[0]
+        sd = None if seed is None else _host(seed, np.float64, nj)
+        if sd is not None and sd.shape[0] != n:
+            raise ValueError(f"seed: {sd.shape[0]} rows for {n} points")
+        ang = np.empty((n, nj), np.float64)
+        it = np.empty(n, np.int32) if want_iters else None
+        tr = np.empty(n, np.int32) if want_tries else None
+        err = np.empty(n, np.float64) if want_fk_err else None
+        self._check(self.lib.ik_chain_solve(self.handle, nj, _ptr(d), _ptr(lo), _ptr(hi), _ptr(p),
+                                            _ptr(sd), n, float(tol), int(max_iter),
+                                            float(damping), int(restarts), _ptr(ang), _ptr(it),
+                                            _ptr(tr), _ptr(err), 0, ctypes.byref(s)))
+        return ang, it, tr, err, s
+
+    def chain_solve_device(self, dh, pts, ang, seed=None, iters=None, tries=None, fk_err=None,
+                           joint_limits=None, tol=1e-6, max_iter=60, damping=1e-3, restarts=0,
+                           flags: int = IK_F_DEVICE):
+        """ik_chain_solve on device tensors (dh and the limits stay host arrays)."""
+        d, lo, hi = self._chain_args(dh, joint_limits, max_iter, restarts)
+        nj = d.shape[1]
+        s = IkStats()
+        n = int(pts.shape[0])
+        args = (self._dev(pts, "float64", (n, 3), "pts"),
+                self._dev(seed, "float64", (n, nj), "seed"),
+                self._dev(ang, "float64", (n, nj), "ang"),
+                self._dev(iters, "int32", (n,), "iters"),
+                self._dev(tries, "int32", (n,), "tries"),
+                self._dev(fk_err, "float64", (n,), "fk_err"))
+        self._on_torch_stream(lambda: self._check(self.lib.ik_chain_solve(
+            self.handle, nj, _ptr(d), _ptr(lo), _ptr(hi), args[0], args[1], n, float(tol),
+            int(max_iter), float(damping), int(restarts), args[2], args[3], args[4], args[5],
+            flags, ctypes.byref(s))))
         return s
 
     # -- analytic (include/ikhip.h "Analytic") ----------------------------------

@@ -27,6 +27,14 @@ point; --verbose then reports the FK round trip and how many pitches were moved.
 the reference's generators (robot/position_generator.py, cli.py:80-229) with the
 same arguments: --to-file writes the x,y,z CSV, --verbose prints the shape's
 parameters as the reference does (its 3-D plot is out of scope).
+`--method chain --dh FILE [--seed-angles FILE] [--joint-limits=...] [--restarts R]
+[--refine-tol FLOAT | --tol FLOAT] [--max-iter INT]` (not in the reference) solves any DH
+chain of 2..8 revolute joints by damped least squares with restarts
+(kinematics/chain.py): FILE is a CSV of four lines (theta, d, a, alpha) with one value
+per joint and no header, the theta line being the home pose that seeds a solve
+without --seed-angles (a CSV with a header row, one angle row per point);
+--joint-limits takes one field per joint here; the angles are written as
+theta1..thetaN.  Defaults: tol 1e-6, 60 steps an attempt, 4 restarts.
 """
 from __future__ import annotations
 
@@ -41,6 +49,8 @@ EXAMPLES = {
     "fabrik": "--inverse-kine --method fabrik --points filename.csv",
     "analytic": "--inverse-kine --method analytic --points filename.csv --pitch -1.5708 "
                 "--elbow up --nearest-pitch",
+    "chain": "--inverse-kine --method chain --dh dh_table.csv --points filename.csv "
+             "--joint-limits=-1.5:1.5,,,,, --restarts 4",
     "circle": "--generate-data --shape circle --radius 3 --samples 20 --center 1,5,2",
     "cube": "--generate-data --shape cube --step 0.75 --dim 2,3,4 --start 1,2,3",
     "cube_random": "--generate-data --shape cube_random --step 0.75 --dim 2,3,4 --start 1,2,3",
@@ -61,7 +71,7 @@ def _parser():
     g = p.add_mutually_exclusive_group()
     g.add_argument("--inverse-kine", action="store_true")
     g.add_argument("--generate-data", action="store_true")
-    p.add_argument("--method", choices=["ann", "fabrik", "analytic"])
+    p.add_argument("--method", choices=["ann", "fabrik", "analytic", "chain"])
     p.add_argument("--shape", choices=list(SHAPE_ARGS))
     p.add_argument("--example", action="store_true")
     p.add_argument("--points", type=str, help=".csv file name with stored trajectory points")
@@ -70,8 +80,14 @@ def _parser():
     p.add_argument("--verbose", action="store_true")
     p.add_argument("--show-path", action="store_true")
     p.add_argument("--separate-plots", action="store_true")
-    p.add_argument("--tol", type=float, default=0.001, help="FABRIK error margin")
-    p.add_argument("--max-iter", type=int, default=100, help="FABRIK iteration cap")
+    p.add_argument("--tol", type=float, default=None,
+                   help="FABRIK error margin (default 0.001); chain: the tolerance (default 1e-6)")
+    p.add_argument("--max-iter", type=int, default=None,
+                   help="FABRIK iteration cap (default 100); chain: steps of one attempt "
+                        "(default 60)")
+    p.add_argument("--dh", type=str, help="chain: CSV of four lines theta, d, a, alpha")
+    p.add_argument("--seed-angles", type=str, help="chain: CSV of one seed row per point")
+    p.add_argument("--restarts", type=int, default=None, help="chain: restarts (default 4)")
     p.add_argument("--device", type=int, default=None, help="GPU index")
     p.add_argument("--refine-tol", type=float, default=None,
                    help="ANN: polish the angles until |FK(theta) - p| <= this")
@@ -113,10 +129,9 @@ def _read_points_pitch(path):
     return df.drop(columns="pitch").values.tolist(), df["pitch"].to_numpy(np.float64)
 
 
-def _save_angles(data, filename):
+def _save_angles(data, filename, nj=4):
     import pandas as pd
-    pd.DataFrame(data, columns=['theta1', 'theta2', 'theta3', 'theta4']).to_csv(filename,
-                                                                                index=False)
+    pd.DataFrame(data, columns=[f'theta{i + 1}' for i in range(nj)]).to_csv(filename, index=False)
 
 
 def _verbose(points, joint_angles):
@@ -130,11 +145,11 @@ def _verbose(points, joint_angles):
           f"over {len(err)} points")
 
 
-def _joint_limits(text, parser):
-    """--joint-limits "lo:hi,lo:hi,,lo:hi": four entries, (lo, hi) or None."""
+def _joint_limits(text, parser, nj=4):
+    """--joint-limits "lo:hi,lo:hi,,lo:hi": nj entries, (lo, hi) or None."""
     fields = text.split(",")
-    if len(fields) != 4:
-        parser.error(f"--joint-limits takes 4 comma-separated fields, got {len(fields)}")
+    if len(fields) != nj:
+        parser.error(f"--joint-limits takes {nj} comma-separated fields, got {len(fields)}")
     out = []
     for i, f in enumerate(fields):
         if not f.strip():
@@ -148,6 +163,64 @@ def _joint_limits(text, parser):
     return out
 
 
+def _chain(args, parser):
+    """--method chain: ChainInverseKinematics on the table of --dh."""
+    from .kinematics.chain import ChainInverseKinematics, chain_dh, chain_fk, chain_limit_arrays
+    from .robot.robot import OutOfRobotReachException
+    if args.dh is None:
+        parser.error("the following arguments are required: --dh")
+    for flag, given in (("--model", args.model is not None), ("--pitch", args.pitch is not None),
+                        ("--elbow", args.elbow is not None), ("--nearest-pitch", args.nearest_pitch)):
+        if given:
+            parser.error(f"{flag} is not valid with --method chain")
+    if args.refine_tol is not None and args.tol is not None:
+        parser.error("--method chain takes --refine-tol or --tol, not both")
+    try:
+        dh = chain_dh(np.loadtxt(args.dh, delimiter=",", ndmin=2))
+    except (OSError, ValueError) as e:
+        parser.error(f"--dh: {e}")
+    nj = dh.shape[1]
+    joint_limits = None
+    if args.joint_limits is not None:
+        joint_limits = _joint_limits(args.joint_limits, parser, nj)
+        try:
+            chain_limit_arrays(joint_limits, nj)
+        except ValueError as e:
+            parser.error(f"--joint-limits: {e}")
+    restarts = 4 if args.restarts is None else args.restarts
+    if not 0 <= restarts <= 255:
+        parser.error("--restarts takes 0..255")
+    tol = args.refine_tol if args.refine_tol is not None else args.tol
+    points = _read_points(args.points)
+    seed = None
+    if args.seed_angles is not None:
+        import pandas as pd
+        seed = pd.read_csv(args.seed_angles).to_numpy(np.float64)
+        if seed.shape != (len(points), nj):
+            parser.error(f"--seed-angles: {seed.shape[0]} rows of {seed.shape[1]} angles for "
+                         f"{len(points)} points of {nj} joints")
+    ik = ChainInverseKinematics(dh, joint_limits, tol=1e-6 if tol is None else tol,
+                                max_iter=60 if args.max_iter is None else args.max_iter,
+                                restarts=restarts)
+    try:
+        joint_angles = ik.ikine(points, seed)
+    except (OutOfRobotReachException, ValueError) as kine_exception:
+        print(str(kine_exception))
+        return 0
+    if args.verbose:
+        err = np.linalg.norm(chain_fk(dh, joint_angles) - np.asarray(points, np.float64), axis=1)
+        it, tries = ik.last_iters, ik.last_tries
+        print(joint_angles)
+        print(f"FK round trip: max |FK(theta) - p| = {err.max():.6g}, mean = {err.mean():.6g} "
+              f"over {len(err)} points")
+        print(f"chain: {nj} joints, tol {ik.tol:g}, max {int(it.max())} steps (mean "
+              f"{it.mean():.3g}), {int((tries > 0).sum())} points solved by a restart, "
+              f"{ik.last_stats.n_capped} not converged")
+    if args.to_file is not None:
+        _save_angles(joint_angles, args.to_file, nj)
+    return 0
+
+
 def _ikine(args, parser):
     from .robot.robot import OutOfRobotReachException
     from .robot.robot import SixDOFRobot as Robot
@@ -158,6 +231,12 @@ def _ikine(args, parser):
         return 0
     if args.points is None:
         parser.error("the following arguments are required: --points")
+    if args.method == "chain":
+        return _chain(args, parser)
+    for flag, given in (("--dh", args.dh is not None), ("--seed-angles", args.seed_angles is not None),
+                        ("--restarts", args.restarts is not None)):
+        if given:
+            parser.error(f"{flag} is only valid with --method chain")
     if args.method == "ann" and args.model is None:
         parser.error("the following arguments are required: --model")
     if args.refine_tol is not None and args.method != "ann":
@@ -197,7 +276,8 @@ def _ikine(args, parser):
         ik.load_model(args.model)
     elif args.method == "fabrik":
         ik = FabrikInverseKinematics(dh, Robot.links_lengths, Robot.effector_workspace_limits,
-                                     args.tol, args.max_iter)
+                                     0.001 if args.tol is None else args.tol,
+                                     100 if args.max_iter is None else args.max_iter)
     try:
         joint_angles = ik.ikine(points)
     except (OutOfRobotReachException, ValueError) as kine_exception:

@@ -879,7 +879,9 @@ int ik_ann_solve(ik_ctx *c, const double *pts, int64_t n, float *ang, double *fk
 }
 
 // ---- refine (ik_refine.hip) ----------------------------------------------------
-static int refine_args(const char *who, ik_ctx *c, int64_t n, bool arrays, double tol,
+}  // extern "C"
+
+int ikapi::refine_args(const char *who, ik_ctx *c, int64_t n, bool arrays, double tol,
                        int32_t max_iter, double damping, const double *ang, int flags) {
   const std::string w(who);
   if (!c || n < 0 || (n > 0 && !arrays) || max_iter < 0) return fail(IK_E_BADARG, w + ": bad args");
@@ -888,6 +890,8 @@ static int refine_args(const char *who, ik_ctx *c, int64_t n, bool arrays, doubl
     return fail(IK_E_BADARG, w + ": damping must be finite and > 0");
   return check_flags(who, flags, ang);
 }
+
+extern "C" {
 
 int ik_refine(ik_ctx *c, const double *pts, const double *seed, int64_t n, double tol,
               int32_t max_iter, double damping, double *ang, int32_t *iters, double *fk_err,

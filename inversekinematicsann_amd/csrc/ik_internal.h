@@ -2,7 +2,7 @@
 // translation units share (ik_api.cpp: single-device calls; ik_pipe.cpp: the
 // chunked host-pointer pipeline; ik_train_api.cpp: the training calls, whose
 // layouts / epoch plan / refusals are the host-only ik_train_plan.cpp;
-// ik_shard.hip: the RCCL-sharded calls, whose plan / tail / histogram arithmetic
+// ik_chain_api.cpp: ik_chain_solve; ik_shard.hip: the RCCL-sharded calls, whose plan / tail / histogram arithmetic
 // is the host-only ik_shard_plan.cpp).  Not installed; include/ikhip.h is the
 // interface.
 #pragma once
@@ -232,6 +232,11 @@ int set_dev(ik_ctx *c);
 // The refusals every enqueueing call shares: IK_F_ASYNC needs IK_F_DEVICE, and a
 // device `ang` (null: the call has none) is stored 16 bytes at a time.
 int check_flags(const char *who, int flags, const void *ang = nullptr);
+// What ik_refine, ik_ann_solve_refined and ik_chain_solve refuse alike (ik_api.cpp): a
+// NULL context, n < 0, missing arrays with n > 0, max_iter < 0, a NaN tol, a damping
+// that is not finite and > 0, then check_flags (ang null: no alignment demanded).
+int refine_args(const char *who, ik_ctx *c, int64_t n, bool arrays, double tol, int32_t max_iter,
+                double damping, const double *ang, int flags);
 void stats_from_dev(const ikhip::DevStats &d, ik_stats *s);
 int finish(ik_ctx *c, int flags, ik_stats *stats);
 // Device pointers only, on the context's stream: stats reset + the solve's kernels.
