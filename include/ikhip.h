@@ -317,6 +317,69 @@ int ik_chain_solve(ik_ctx *ctx, int nj, const double *dh /*host, 4 x nj: theta, 
                    double *ang /*n x nj*/, int32_t *iters /*nullable*/, int32_t *tries /*nullable*/,
                    double *fk_err /*nullable*/, int flags, ik_stats *stats);
 
+/* ---- Chain pose solve ----------------------------------------------------------
+ * ik_chain_solve for a tool pose: position and orientation in one damped
+ * least-squares step, float64, NJ = nj (2..8) revolute joints.  A goal is pts[i] (3)
+ * and rot[i], a 3 x 3 matrix G, row-major, 9 doubles: the pose ik_fk_chain reports as
+ * its last cumulative transform, p = M_nj[:3, 3], G = M_nj[:3, :3].  G is used as
+ * given, with no orthonormalisation and no check.  dh, lo, hi, seed, ang, iters, tries,
+ * the constants, the limits, the seed, the update and the start points of the restarts
+ * are "Chain solve"'s; rot n x 9 and rot_err (nullable) n float64 follow the same
+ * host / IK_F_DEVICE / IK_F_ASYNC convention, and no alignment is demanded.  Per row:
+ *   chain: "Chain solve"'s loop, whose effector and linear columns are computed by the
+ *     same operations in the same order (the same bits), with two more kinds of
+ *     passenger in a second pass of the same loop.  Tool frame: three direction vectors
+ *     start as the columns of Rx(alpha_NJ), (1, 0, 0), (0, ca, sa), (0, -sa, ca); they
+ *     take every Rz(t_i) (vx = c x - s y, vy = s x + c y) and every Rx(alpha_i)
+ *     (vy = ca y - sa z, vz = sa y + ca z) and no translation, and end as the columns
+ *     r_0, r_1, r_2 of R(theta).  Axis i is opened as (0, 0, 1) when joint i is
+ *     reached, where Rz(t_i) leaves it alone, and from then on takes only the rotations
+ *     to its left, as linear column i does; axis 1 is identically (0, 0, 1).
+ *   errors: ep = sqrt(ex^2 + ey^2 + ez^2), e = p - x, as in "Chain solve".
+ *     For the step, e_w = 1/2 sum_k r_k x g_k (g_k the columns of G), sin(phi) axis in
+ *     the base frame: entry m is 0.5 (((k = 0) + (k = 1)) + (k = 2)), a term being
+ *     r_k[a] g_k[b] - r_k[b] g_k[a], (a, b) = (1, 2), (2, 0), (0, 1) for m = 0, 1, 2.
+ *     For stopping and reporting, er = sqrt(0.5 sum_ij (R_ij - G_ij)^2), the sum
+ *     row-major from (0, 0): 2 sin(phi / 2) for an orthonormal G.  The stop rule does
+ *     not use |e_w|, which is zero at phi = pi.
+ *   matrix: J' is 6 x NJ, rows 0..2 the linear ones, rows 3..5 w times the axes
+ *     (w = rot_weight), the locked columns replaced by +0.0; e' = (e, w e_w);
+ *     A = J' J'^T + damping^2 I, 21 entries, A_ij = sum_k J'_ik J'_jk over the joints in
+ *     joint order from joint 1's term -- an entry of row 2, whose joint-1 value is
+ *     identically zero, from joint 2's, as in "Chain solve" -- damping^2 added last on
+ *     the diagonal.
+ *   solve: LDL^T without pivoting,
+ *       u_ij = A_ij - sum_{k<j} l_ik u_jk  (k ascending; u_jj = D_j),  l_ij = u_ij / D_j
+ *       y_i = e'_i - sum_{k<i} l_ik y_k
+ *       q_i = y_i / D_i - sum_{k>i} l_ki q_k  (k ascending)
+ *       delta_k = sum_r J'_rk q_r  (r ascending from 0; joint 1 without r = 2)
+ *     then "Chain solve"'s update and its active-set loop under limits.
+ *   attempts: nan = ep or er is NaN; above = ep > tol || er > rot_tol.  An attempt ends
+ *     when !above || nan || it == max_iter, and restarts when above && !nan &&
+ *     a < restarts.  The row returns the attempt with the smallest score = ep + w er,
+ *     the earliest on a tie (a NaN score never replaces the held one): its angles go
+ *     to ang, ep to fk_err, er to rot_err, its index to tries.  Some |alpha_i| > 2 pi:
+ *     both errors are NaN and no row takes a step.
+ * With rot_weight = 0, rot_tol = +inf and a finite G every rotational term of the solve
+ * is an exact zero, and ang, iters, tries and fk_err are ik_chain_solve's bit for bit.
+ * stats: max_iters / sum_iters over iters, n_capped = rows with !(fk_err <= tol &&
+ * rot_err <= rot_tol), first_err the lowest such row with both errors finite
+ * (IK_E_OUT_OF_REACH; -1: none), max_fk_err / sum_fk_err over the finite position
+ * errors, first_oob always -1.  Plain damped least squares on a chain that is not
+ * redundant for a pose (6 joints and fewer) leaves rows stuck far from the seed;
+ * restarts are the remedy and multiply the worst row's steps.
+ * IK_E_BADARG, the context left usable: what ik_chain_solve refuses, a NULL rot with
+ * n > 0, rot_tol NaN, rot_weight NaN, infinite or < 0.  n == 0 is IK_OK with empty
+ * stats. */
+int ik_chain_pose_solve(ik_ctx *ctx, int nj, const double *dh /*host, 4 x nj: theta, d, a, alpha*/,
+                        const double *lo /*host nj, nullable*/, const double *hi /*host nj, nullable*/,
+                        const double *pts /*n x 3*/, const double *rot /*n x 9*/,
+                        const double *seed /*n x nj, nullable*/, int64_t n, double tol,
+                        double rot_tol, double rot_weight, int32_t max_iter, double damping,
+                        int32_t restarts, double *ang /*n x nj*/, int32_t *iters /*nullable*/,
+                        int32_t *tries /*nullable*/, double *fk_err /*nullable*/,
+                        double *rot_err /*nullable*/, int flags, ik_stats *stats);
+
 /* ---- Analytic ----------------------------------------------------------------
  * Closed-form inverse kinematics with a chosen tool pitch and elbow branch, float64,
  * no iteration, for a context's robot that is a yaw joint followed by a planar

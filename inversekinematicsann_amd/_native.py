@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = ("ik_ctx_create", "ik_ctx_destroy", "ik_ctx_set_stream", "ik_
                     "ik_set_joint_limits", "ik_get_joint_limits", "ik_check_joint_limits",
                     "ik_fabrik_solve", "ik_fabrik_solve_fk", "ik_fabrik_calc", "ik_fabrik_reset_order", "ik_ann_load", "ik_ann_solve",
                     "ik_refine", "ik_ann_solve_refined", "ik_analytic_solve", "ik_chain_solve",
+                    "ik_chain_pose_solve",
                     "ik_stats_fetch", "ik_ctx_set_timing", "ik_kernel_times",
                     "ik_ctx_set_debug", "ik_debug_read", "ik_ann_set_mode", "ik_ann_get_mode",
                     "ik_ann_effective_mode",
@@ -146,6 +147,10 @@ def load_library(path: str = LIB_PATH):
                                         st]
         L.ik_chain_solve.argtypes = [vp, ctypes.c_int, dp, dp, dp, dp, dp, i64, ctypes.c_double,
                                      i32, ctypes.c_double, i32, dp, ip, ip, dp, ctypes.c_int, st]
+        L.ik_chain_pose_solve.argtypes = [vp, ctypes.c_int, dp, dp, dp, dp, dp, dp, i64,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_double, i32,
+                                          ctypes.c_double, i32, dp, ip, ip, dp, dp, ctypes.c_int,
+                                          st]
         L.ik_stats_fetch.argtypes = [vp, st]
         L.ik_ctx_sync.argtypes = [vp]
         L.ik_comm_set_timeout.argtypes = [vp, ctypes.c_double]
@@ -685,6 +690,65 @@ class Context:
             self.handle, nj, _ptr(d), _ptr(lo), _ptr(hi), args[0], args[1], n, float(tol),
             int(max_iter), float(damping), int(restarts), args[2], args[3], args[4], args[5],
             flags, ctypes.byref(s))))
+        return s
+
+    # -- chain pose solve (include/ikhip.h "Chain pose solve") --------------------
+    def chain_pose_solve(self, dh, pts, rot, seed=None, joint_limits=None, tol=1e-6, rot_tol=None,
+                         rot_weight=1.0, max_iter=60, damping=1e-3, restarts=0, want_iters=True,
+                         want_tries=True, want_fk_err=True, want_rot_err=True):
+        """ik_chain_pose_solve on host arrays: chain_solve's arguments plus rot n x 3 x 3
+        (or n x 9, row-major), the goal orientations, rot_tol (None: tol) and rot_weight.
+        Returns (angles n x nj f64, iters, tries, fk_err, rot_err, stats)."""
+        from .kinematics.chain import check_pose_weights
+        d, lo, hi = self._chain_args(dh, joint_limits, max_iter, restarts)
+        rot_tol = tol if rot_tol is None else rot_tol
+        check_pose_weights(rot_tol, rot_weight)
+        nj = d.shape[1]
+        s = IkStats()
+        p = _host(pts, np.float64, 3)
+        n = p.shape[0]
+        g = _host(np.asarray(rot, np.float64).reshape(-1, 9), np.float64, 9)
+        if g.shape[0] != n:
+            raise ValueError(f"rot: {g.shape[0]} rotations for {n} points")
+        sd = None if seed is None else _host(seed, np.float64, nj)
+        if sd is not None and sd.shape[0] != n:
+            raise ValueError(f"seed: {sd.shape[0]} rows for {n} points")
+        ang = np.empty((n, nj), np.float64)
+        it = np.empty(n, np.int32) if want_iters else None
+        tr = np.empty(n, np.int32) if want_tries else None
+        err = np.empty(n, np.float64) if want_fk_err else None
+        rerr = np.empty(n, np.float64) if want_rot_err else None
+        self._check(self.lib.ik_chain_pose_solve(
+            self.handle, nj, _ptr(d), _ptr(lo), _ptr(hi), _ptr(p), _ptr(g), _ptr(sd), n, float(tol),
+            float(rot_tol), float(rot_weight), int(max_iter), float(damping), int(restarts),
+            _ptr(ang), _ptr(it), _ptr(tr), _ptr(err), _ptr(rerr), 0, ctypes.byref(s)))
+        return ang, it, tr, err, rerr, s
+
+    def chain_pose_solve_device(self, dh, pts, rot, ang, seed=None, iters=None, tries=None,
+                                fk_err=None, rot_err=None, joint_limits=None, tol=1e-6,
+                                rot_tol=None, rot_weight=1.0, max_iter=60, damping=1e-3,
+                                restarts=0, flags: int = IK_F_DEVICE):
+        """ik_chain_pose_solve on device tensors (dh and the limits stay host arrays);
+        rot is n x 9."""
+        from .kinematics.chain import check_pose_weights
+        d, lo, hi = self._chain_args(dh, joint_limits, max_iter, restarts)
+        rot_tol = tol if rot_tol is None else rot_tol
+        check_pose_weights(rot_tol, rot_weight)
+        nj = d.shape[1]
+        s = IkStats()
+        n = int(pts.shape[0])
+        args = (self._dev(pts, "float64", (n, 3), "pts"),
+                self._dev(rot, "float64", (n, 9), "rot"),
+                self._dev(seed, "float64", (n, nj), "seed"),
+                self._dev(ang, "float64", (n, nj), "ang"),
+                self._dev(iters, "int32", (n,), "iters"),
+                self._dev(tries, "int32", (n,), "tries"),
+                self._dev(fk_err, "float64", (n,), "fk_err"),
+                self._dev(rot_err, "float64", (n,), "rot_err"))
+        self._on_torch_stream(lambda: self._check(self.lib.ik_chain_pose_solve(
+            self.handle, nj, _ptr(d), _ptr(lo), _ptr(hi), args[0], args[1], args[2], n, float(tol),
+            float(rot_tol), float(rot_weight), int(max_iter), float(damping), int(restarts),
+            args[3], args[4], args[5], args[6], args[7], flags, ctypes.byref(s))))
         return s
 
     # -- analytic (include/ikhip.h "Analytic") ----------------------------------

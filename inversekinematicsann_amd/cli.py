@@ -35,6 +35,12 @@ per joint and no header, the theta line being the home pose that seeds a solve
 without --seed-angles (a CSV with a header row, one angle row per point);
 --joint-limits takes one field per joint here; the angles are written as
 theta1..thetaN.  Defaults: tol 1e-6, 60 steps an attempt, 4 restarts.
+`--method chain --poses FILE [--rot-tol FLOAT] [--rot-weight FLOAT]` takes tool poses in
+place of --points: a CSV with the header x,y,z,r11,r12,r13,r21,...,r33, the position and
+the rotation matrix row by row (ChainInverseKinematics.ikine_pose); --rot-tol (default:
+the tolerance) bounds the rotation error sqrt(1/2 |R - G|_F^2) of a solved pose,
+--rot-weight (default 1) weighs the rotation rows of the step; --verbose adds the
+largest rotation error.
 """
 from __future__ import annotations
 
@@ -88,6 +94,12 @@ def _parser():
     p.add_argument("--dh", type=str, help="chain: CSV of four lines theta, d, a, alpha")
     p.add_argument("--seed-angles", type=str, help="chain: CSV of one seed row per point")
     p.add_argument("--restarts", type=int, default=None, help="chain: restarts (default 4)")
+    p.add_argument("--poses", type=str,
+                   help="chain: CSV x,y,z,r11,..,r33 of tool poses, in place of --points")
+    p.add_argument("--rot-tol", type=float, default=None,
+                   help="chain with --poses: the rotation tolerance (default: the tolerance)")
+    p.add_argument("--rot-weight", type=float, default=None,
+                   help="chain with --poses: weight of the rotation rows (default 1)")
     p.add_argument("--device", type=int, default=None, help="GPU index")
     p.add_argument("--refine-tol", type=float, default=None,
                    help="ANN: polish the angles until |FK(theta) - p| <= this")
@@ -163,6 +175,19 @@ def _joint_limits(text, parser, nj=4):
     return out
 
 
+POSE_COLUMNS = ["x", "y", "z"] + [f"r{i}{j}" for i in (1, 2, 3) for j in (1, 2, 3)]
+
+
+def _read_poses(path, parser):
+    """--poses: (points n x 3, rotations n x 3 x 3) of a CSV with POSE_COLUMNS."""
+    import pandas as pd
+    df = pd.read_csv(path)
+    if list(df.columns) != POSE_COLUMNS:
+        parser.error("--poses: the header must be " + ",".join(POSE_COLUMNS))
+    v = df.to_numpy(np.float64)
+    return v[:, :3].copy(), v[:, 3:].reshape(-1, 3, 3).copy()
+
+
 def _chain(args, parser):
     """--method chain: ChainInverseKinematics on the table of --dh."""
     from .kinematics.chain import ChainInverseKinematics, chain_dh, chain_fk, chain_limit_arrays
@@ -175,6 +200,16 @@ def _chain(args, parser):
             parser.error(f"{flag} is not valid with --method chain")
     if args.refine_tol is not None and args.tol is not None:
         parser.error("--method chain takes --refine-tol or --tol, not both")
+    if args.poses is not None and args.points is not None:
+        parser.error("--method chain takes --points or --poses, not both")
+    for flag, given in (("--rot-tol", args.rot_tol is not None),
+                        ("--rot-weight", args.rot_weight is not None)):
+        if given and args.poses is None:
+            parser.error(f"{flag} is only valid with --poses")
+    if args.rot_tol is not None and np.isnan(args.rot_tol):
+        parser.error("--rot-tol takes a number")
+    if args.rot_weight is not None and not (np.isfinite(args.rot_weight) and args.rot_weight >= 0):
+        parser.error("--rot-weight takes a finite number >= 0")
     try:
         dh = chain_dh(np.loadtxt(args.dh, delimiter=",", ndmin=2))
     except (OSError, ValueError) as e:
@@ -191,7 +226,10 @@ def _chain(args, parser):
     if not 0 <= restarts <= 255:
         parser.error("--restarts takes 0..255")
     tol = args.refine_tol if args.refine_tol is not None else args.tol
-    points = _read_points(args.points)
+    if args.poses is not None:
+        points, rotations = _read_poses(args.poses, parser)
+    else:
+        points = _read_points(args.points)
     seed = None
     if args.seed_angles is not None:
         import pandas as pd
@@ -201,9 +239,13 @@ def _chain(args, parser):
                          f"{len(points)} points of {nj} joints")
     ik = ChainInverseKinematics(dh, joint_limits, tol=1e-6 if tol is None else tol,
                                 max_iter=60 if args.max_iter is None else args.max_iter,
-                                restarts=restarts)
+                                restarts=restarts, rot_tol=args.rot_tol,
+                                rot_weight=1.0 if args.rot_weight is None else args.rot_weight)
     try:
-        joint_angles = ik.ikine(points, seed)
+        if args.poses is not None:
+            joint_angles = ik.ikine_pose((points, rotations), seed)
+        else:
+            joint_angles = ik.ikine(points, seed)
     except (OutOfRobotReachException, ValueError) as kine_exception:
         print(str(kine_exception))
         return 0
@@ -216,6 +258,9 @@ def _chain(args, parser):
         print(f"chain: {nj} joints, tol {ik.tol:g}, max {int(it.max())} steps (mean "
               f"{it.mean():.3g}), {int((tries > 0).sum())} points solved by a restart, "
               f"{ik.last_stats.n_capped} not converged")
+        if args.poses is not None:
+            print(f"rotation error: max sqrt(1/2 |R - G|_F^2) = {np.nanmax(ik.last_rot_err):.6g} "
+                  f"(rot-tol {ik.rot_tol:g}, rot-weight {ik.rot_weight:g})")
     if args.to_file is not None:
         _save_angles(joint_angles, args.to_file, nj)
     return 0
@@ -229,12 +274,14 @@ def _ikine(args, parser):
     if args.example:
         print(EXAMPLES[args.method])
         return 0
-    if args.points is None:
+    if args.points is None and not (args.method == "chain" and args.poses is not None):
         parser.error("the following arguments are required: --points")
     if args.method == "chain":
         return _chain(args, parser)
     for flag, given in (("--dh", args.dh is not None), ("--seed-angles", args.seed_angles is not None),
-                        ("--restarts", args.restarts is not None)):
+                        ("--restarts", args.restarts is not None), ("--poses", args.poses is not None),
+                        ("--rot-tol", args.rot_tol is not None),
+                        ("--rot-weight", args.rot_weight is not None)):
         if given:
             parser.error(f"{flag} is only valid with --method chain")
     if args.method == "ann" and args.model is None:

@@ -218,7 +218,7 @@ class Stage {
     bool staged;  // lives in the scratch at `off`
     void *dev;
   };
-  static constexpr int kMax = 6;  // (ik_ann_solve_refined)
+  static constexpr int kMax = 8;  // (ik_chain_pose_solve)
   int add(Kind kind, const void *user, size_t bytes);
   ik_ctx *c_;
   bool dev_;
